@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark: device-resident batch CityHash64 on 64-byte keys (BASELINE.json).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
                   [--config cfg1|cfg2|cfg3|cfg4|cfg5|place|bucket|exchange|records|xrecords|long]
+
+A plain run does what the headline figure needs and nothing else: it sets up
+the keys, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given and prints the line (contract fields, ms_per_step and
+the roofline figures that follow from the timed steps themselves).  `--full`
+adds every other leg described below: the configs[4] block, the calibrated
+streams of the roofline block, cpu_baseline, host_resident, per_rank and
+parity.
 
 One step = one pass of the hot path (one kernel launch) over this GPU's batch
 of synthetic keys already resident in HBM.  Default workload = BASELINE
@@ -15,13 +23,14 @@ collective on the data path (weak scaling); the only collectives are the
 timing barrier, the max of elapsed times and the parity reductions.
 "cfg5" = 128M keys per GPU, i.e. BASELINE configs[4] (1B keys) at N = 8.
 
-The default run also times BASELINE configs[4] at its own N: the 1B x 64 B
+The default config's --full run also times BASELINE configs[4] at its own N: the 1B x 64 B
 stream split contiguously over the N ranks (1B/N keys per GPU, strong
 scaling; "baseline_config4" block, parity from the committed 16M-key chunk
 folds).  `--dist-backend gloo` rehearses the N-rank path on fewer GPUs (ranks
 share devices; RCCL refuses two ranks on one GPU).
 
-Rank 0 prints one JSON line.  Besides the contract fields it carries
+Rank 0 prints one JSON line.  Besides the contract fields it carries (all but
+the first part of roofline only with --full)
   roofline      -- achieved algorithmic HBM GB/s of the hash kernel (72 B/key:
                    64 B key read + 8 B digest write) over its average step
                    time: one pair of HIP events on the launch stream around
@@ -93,6 +102,16 @@ def parse():
                          "collectives (and the exchange of the exchange/xrecords configs) run through it")
     ap.add_argument("--no-config4", action="store_true",
                     help="skip the BASELINE configs[4] block (1B x 64 B keys split over the N ranks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg of the line: the parity check against "
+                         "the reference folds, the calibrated read/key streams of the roofline block, the "
+                         "host-resident rate, the CPU baseline, the per-rank block, cfg1's wrapper path and (default "
+                         "config) the BASELINE configs[4] block.  Without it the run sets up, warms up, times the "
+                         "steps and prints the line with the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (the arrays its caller "
+                         "receives) as DIR/<name>.npy in float64/float32, a fixed seeded sample of the rows of a "
+                         "large array (at most 64 MB in all); <name>.rank<r>.npy for ranks r > 0")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check only: every rank joins a gloo group, touches no GPU and rank 0 "
                          "prints one JSON line with the world (tests/test_bench_launch.py)")
@@ -170,12 +189,12 @@ CONFIG4_KEYS = 1 << 30  # BASELINE configs[4]: 1B x 64 B keys over the node's GP
 def plan(a, world: int) -> dict:
     """What this run measures, decided before any GPU work (printed by
     --dry-run, so the CPU tests can check it): the per-GPU workload of
-    `value` and, for the default config, the BASELINE configs[4] block -- the
-    1B x 64 B stream split over the N ranks (strong scaling), timed beside
-    the cfg2 weak-scaling value at every N."""
+    `value` and, for a --full run of the default config, the BASELINE
+    configs[4] block -- the 1B x 64 B stream split over the N ranks (strong
+    scaling), timed beside the cfg2 weak-scaling value at every N."""
     p = {"config": a.config, "value_scaling": "strong" if a.config == "config4" else "weak",
          "world_size": world, "backend": a.dist_backend}
-    if a.config == "cfg2" and not a.no_config4 and not a.keys_per_gpu:
+    if a.config == "cfg2" and a.full and not a.no_config4 and not a.keys_per_gpu:
         p["config4"] = {"keys_total": CONFIG4_KEYS, "key_bytes": 64, "split": "strong (contiguous, 1B/N per rank)",
                         "keys_per_rank": [CONFIG4_KEYS * (r + 1) // world - CONFIG4_KEYS * r // world
                                           for r in range(world)]}
@@ -207,6 +226,51 @@ def flush_infinity_cache(torch, dev):
     scratch.fill_(0x5A)
     torch.cuda.synchronize()
     del scratch
+
+
+DUMP_BYTES = 48 << 20  # all files of one --dump-outputs together (the limit is 64 MB), split evenly over the arrays
+DUMP_SEED = 0x0D0C5EED
+
+
+def dump_outputs(torch, path: str, arrays: dict, rank: int = 0) -> dict:
+    """Write the tensors of `arrays` (name -> tensor or None) as
+    <path>/<name>.npy (<name>.rank<r>.npy for rank r > 0) so that two builds
+    can be compared value for value.  Every value is stored exactly: a 64-bit
+    integer column becomes two float64 columns (its high and low 32 bits, both
+    as unsigned numbers), narrower integers one float64 column, bytes float32.
+    An array whose rows would exceed its share of DUMP_BYTES is cut to a
+    fixed sample of its rows: the first and the last row and rows drawn by a
+    generator seeded with DUMP_SEED (the same rows in every run of the same
+    shape, in increasing order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: t for k, t in arrays.items() if torch.is_tensor(t)}
+    share = DUMP_BYTES // max(1, len(arrays))
+    done, total = {}, 0
+    for name, t in arrays.items():
+        t = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+        rows, cols = t.shape
+        wide = t.dtype == torch.int64
+        cell = 4 if t.dtype == torch.uint8 else (16 if wide else 8)
+        keep = max(2, share // (cell * max(cols, 1)))
+        if rows > keep:
+            pick = np.random.default_rng(DUMP_SEED).integers(0, rows, size=keep - 2)
+            idx = np.unique(np.concatenate(([0, rows - 1], pick)))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        h = t.cpu().numpy()
+        if wide:
+            u = h.view(np.uint64)
+            h = np.stack([(u >> np.uint64(32)).astype(np.float64),
+                          (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1).reshape(h.shape[0], 2 * cols)
+        elif h.dtype == np.uint8:
+            h = h.astype(np.float32)
+        else:
+            h = h.astype(np.float64)
+        f = os.path.join(path, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy")
+        np.save(f, h)
+        total += h.nbytes
+        done[name] = {"file": os.path.basename(f), "rows": int(h.shape[0]), "of": int(rows), "dtype": str(h.dtype)}
+    assert total <= 64 * 10 ** 6, total
+    return {"dir": path, "bytes": total, "arrays": done}
 
 
 def golden_folds():
@@ -471,10 +535,29 @@ def main():
     kern_ms = ev0.elapsed_time(ev1) / a.steps
     elapsed_max, kern_ms_max = D.allreduce_max([elapsed, kern_ms], device=cdev)
 
+    # what the last timed step handed its caller, before any other leg runs
+    # (cfg1's wrapper leg and the parity call write the same buffers again)
+    dumped = None
+    if a.dump_outputs:
+        if bucketed is not None:
+            last = {k: bucketed.get(k) for k in ("rec", "ko", "mb", "pt", "ix", "offs")}
+            last.update({f"x{i}": t for i, t in enumerate(bucketed.get("x", ()))})
+            names = {"rec": "records", "ko": "keys_out", "mb": "mbits", "pt": "ptindex", "ix": "index",
+                     "offs": "offsets", "x0": "exchanged_0", "x1": "exchanged_1", "x2": "exchanged_2",
+                     "x3": "exchanged_3"}
+            last = {names[k]: t for k, t in last.items()}
+        elif cfg in ("cfg1", "place"):
+            last = {"mbits": outs[0], "ptindex": outs[1], "rank": outs[2], "hist": hist}
+        elif cfg == "cfg2r":  # the buffer the last step wrote (next(turn) is the one after it)
+            last = {"digests": rot[(next(turn) - 1) % len(rot)]}
+        else:
+            last = {"digests": out}
+        dumped = dump_outputs(torch, a.dump_outputs, last, rank)
+
     # cfg1's step is the bound C call; the Python mirror's place_batch (its
     # checks and pointer lookups on every call) timed the same way beside it
     wrapper = None
-    if cfg == "cfg1":
+    if cfg == "cfg1" and a.full:
         wturn = [0]
 
         def wstep():
@@ -498,7 +581,7 @@ def main():
 
     # -------------------------------------------- achievable read stream ---
     calib = None
-    if keys is not None:
+    if keys is not None and a.full:
         P.read_stream(keys, True)
         cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(10)]
@@ -511,7 +594,9 @@ def main():
         calib = round(keys.numel() / (cms / 1e3) / 1e9, 1)
     # the 64-B kernel's own data movement with the hash replaced by an XOR fold
     calib_key = None
-    if cfg in ("cfg2", "cfg2r", "cfg5", "config4"):
+    if not a.full:
+        pass
+    elif cfg in ("cfg2", "cfg2r", "cfg5", "config4"):
         fold = torch.empty(n, dtype=torch.int64, device=dev)
         P.key_stream(keys, out=fold)
         cev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -539,7 +624,9 @@ def main():
         del fold
 
     # ------------------------------------------------------------ parity ---
-    if bucketed is not None and bucketed.get("records"):
+    if not a.full:
+        parity = None
+    elif bucketed is not None and bucketed.get("records"):
         parity = check_records(P, torch, D, sh, keys, bucketed, dev, cdev)
     elif bucketed is not None:
         parity = check_buckets(P, torch, D, sh, keys, bucketed, dev, cdev)
@@ -587,18 +674,21 @@ def main():
                      "read_only_GBps": round(total_bytes_in / (kern_ms / 1e3) / 1e9, 1),
                      "calibrated_read_stream_GBps": calib,
                      "calibrated_key_stream_GBps": calib_key},
-        "parity": parity,
+        "full": a.full,
+        **({"parity": parity} if a.full else {}),
     }
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if wrapper is not None:
         res["cfg1_wrapper_path"] = wrapper
-    if world > 1 or dist.is_initialized():
+    if a.full and (world > 1 or dist.is_initialized()):
         res["per_rank"] = D.per_rank_report(rank, local, world, n, bytes_per_key, kern_ms, elapsed, a.steps,
                                             PEAK_HBM_GBPS, device=dev)
-    if cfg in ("cfg2", "cfg3", "cfg4", "cfg5", "cfg1") and not a.no_host:  # (cfg2r: the same host path as cfg2)
+    if a.full and cfg in ("cfg2", "cfg3", "cfg4", "cfg5", "cfg1") and not a.no_host:  # (cfg2r: the host path of cfg2)
         hr = host_rate(P, torch, n, cfg, D, dev, cdev, var=(data, offs, out) if cfg == "cfg3" else None)
         if rank == 0:
             res["host_resident"] = hr
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # The reference city.c on this node's host cores, in the same run at
         # every N: rank 0 alone, after every rank's GPU leg has finished and
         # while the others sleep in a blocking (gloo) barrier, so no rank is

@@ -20,6 +20,7 @@ the two modulo reductions of hash.c:27 and :29 done in Python.
   python tests/golden/gen_golden.py --multirank # + per-rank cfg1/cfg3/cfg4 folds of the
                                              #   N > 1 weak-scaling shards (added)
   python tests/golden/gen_golden.py --bucket-world  # + exchange/xrecords folds (nranks = N)
+  python tests/golden/gen_golden.py --fuzz   # + random keys and their reference digests (npz)
 """
 from __future__ import annotations
 
@@ -352,9 +353,31 @@ def folds_multirank(ranks: int = 8) -> dict:
     return out
 
 
+def fuzz_vectors(R) -> dict:
+    """Random keys of every length 0..299 and around the 512/900/1200-byte
+    thresholds, with the reference's CityHash64 / CityHashCrc128 / CityHash128
+    of each (tests/test_oracle_golden.py checks the oracle against them where
+    oracle/_ref cannot be built)."""
+    rng = np.random.default_rng(7)
+    lens = list(range(0, 300)) + [511, 512, 513, 899, 900, 901, 902, 1199, 1200, 1201, 3000]
+    keys, d64, crc, d128 = [], [], [], []
+    for L in lens:
+        k = rng.integers(0, 256, L, dtype=np.uint8)
+        d = k.tobytes()
+        keys.append(k)
+        d64.append(R.CityHash64(d, L))
+        crc.append(u128(R.CityHashCrc128(d, L)))
+        d128.append(u128(R.CityHash128(d, L)))
+    return {"fuzz_lens": np.array(lens, dtype=np.uint64), "fuzz_bytes": np.concatenate(keys),
+            "fuzz_city64": np.array(d64, dtype=np.uint64), "fuzz_crc128": np.array(crc, dtype=np.uint64),
+            "fuzz_city128": np.array(d128, dtype=np.uint64)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
+    ap.add_argument("--fuzz", action="store_true",
+                    help="add the random-key vectors of the oracle-vs-reference cross-check (npz)")
     ap.add_argument("--extra", action="store_true",
                     help="add the place/bucket/long folds to config_folds.json")
     ap.add_argument("--r02", action="store_true",
@@ -370,6 +393,14 @@ def main():
     R = O.ref()
     if R is None:
         sys.exit("oracle/_ref not built: /root/reference is required to regenerate fixtures")
+    if a.fuzz:
+        npz = os.path.join(HERE, "city_golden.npz")
+        with np.load(npz, allow_pickle=False) as z:
+            vec = {k: z[k] for k in z.files}
+        vec.update(fuzz_vectors(R))
+        np.savez_compressed(npz, **vec)
+        print("added the random-key cross-check vectors")
+        return
     if a.multirank:
         path = os.path.join(HERE, "config_folds.json")
         with open(path) as f:

@@ -28,7 +28,7 @@ def _json_lines(out):
 
 
 def test_gpus_2_launches_two_ranks():
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run"], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--dry-run"], capture_output=True, text=True,
                        timeout=300, env=_env())
     assert p.returncode == 0, p.stderr[-2000:]
     lines = _json_lines(p.stdout)
@@ -40,7 +40,7 @@ def test_gpus_2_launches_two_ranks():
     assert sorted(x["local_rank"] for x in r["ranks"]) == [0, 1]
     pids = {x["pid"] for x in r["ranks"]}
     assert len(pids) == 2                       # two processes, one per rank
-    # the default N > 1 run also times BASELINE configs[4]: 1B x 64 B keys split
+    # the default N > 1 --full run also times BASELINE configs[4]: 1B x 64 B keys split
     # over the ranks (strong scaling), beside the cfg2 weak-scaling value
     c4 = r["plan"]["config4"]
     assert r["plan"]["config"] == "cfg2" and r["plan"]["value_scaling"] == "weak"
@@ -54,7 +54,8 @@ def test_config4_split_is_whole_reference_chunks():
     import bench
     folds = bench.golden_folds()
     for world in (1, 2, 4, 8):
-        a = type("A", (), {"config": "cfg2", "no_config4": False, "keys_per_gpu": 0, "dist_backend": "nccl"})
+        a = type("A", (), {"config": "cfg2", "full": True, "no_config4": False, "keys_per_gpu": 0,
+                           "dist_backend": "nccl"})
         per = bench.plan(a, world)["config4"]["keys_per_rank"]
         assert sum(per) == 1 << 30
         first = 0
@@ -73,9 +74,10 @@ def test_config4_split_is_whole_reference_chunks():
 def test_config4_block_only_on_default_workload():
     sys.path.insert(0, ROOT)
     import bench
-    mk = lambda **kw: type("A", (), {"config": "cfg2", "no_config4": False, "keys_per_gpu": 0,  # noqa: E731
-                                     "dist_backend": "nccl", **kw})
+    mk = lambda **kw: type("A", (), {"config": "cfg2", "full": True, "no_config4": False,  # noqa: E731
+                                     "keys_per_gpu": 0, "dist_backend": "nccl", **kw})
     assert "config4" in bench.plan(mk(), 1)
+    assert "config4" not in bench.plan(mk(full=False), 1)  # a plain run times its own steps only
     assert "config4" not in bench.plan(mk(config="cfg3"), 2)
     assert "config4" not in bench.plan(mk(no_config4=True), 2)
     assert "config4" not in bench.plan(mk(keys_per_gpu=1000), 2)

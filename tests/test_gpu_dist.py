@@ -49,9 +49,10 @@ def test_rccl_world1_exchange_and_reductions():
 def test_bench_nccl_world1_xrecords():
     """bench.py's nccl branch at N = 1: the xrecords step buckets 1M keys by
     the world size into wire records and ships them with one all-to-all(v)
-    through RCCL inside every timed step; the line's parity check verifies
-    the received records."""
+    through RCCL inside every timed step; the --full line's parity check
+    verifies the received records."""
     r = _child([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--config", "xrecords", "--dist-backend",
-                "nccl", "--steps", "3", "--warmup", "1", "--keys-per-gpu", str(1 << 20), "--no-cpu-baseline"], 110)
+                "nccl", "--steps", "3", "--warmup", "1", "--keys-per-gpu", str(1 << 20), "--no-cpu-baseline",
+                "--full"], 110)
     assert r["per_rank"]["backend"] == "nccl" and r["n_gpus"] == 1
     assert "exchange:" in r["parity"] and "FAILED" not in r["parity"], r["parity"]

@@ -134,19 +134,29 @@ def test_fold(oracle):
     assert oracle.fold64(d, 10) == 1 * 21 + 2 * 23 + 3 * 25
 
 
-def test_oracle_matches_compiled_reference_fuzz(oracle):
-    """Cross-check against oracle/_ref (the reference compiled here), if built."""
+def test_oracle_matches_compiled_reference_fuzz(oracle, golden):
+    """Cross-check against the compiled reference on random keys of every
+    length 0..299 and around the 512/900/1200-byte thresholds: the keys and
+    the reference's digests of them are recorded in city_golden.npz
+    (gen_golden.py --fuzz); where oracle/_ref is built, the reference itself
+    is called on the same keys as well."""
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built (no /root/reference)")
-    rng = np.random.default_rng(7)
-    for L in list(range(0, 300)) + [511, 512, 513, 899, 900, 901, 902, 1199, 1200, 1201, 3000]:
-        d = rng.integers(0, 256, L, dtype=np.uint8).tobytes()
-        assert oracle.city64(d) == R.CityHash64(d, L)
-        r = R.CityHashCrc128(d, L)
-        assert oracle.citycrc128(d) == (r.first, r.second)
-        r = R.CityHash128(d, L)
-        assert oracle.city128(d) == (r.first, r.second)
+    lens = [int(x) for x in golden["fuzz_lens"]]
+    assert lens == list(range(0, 300)) + [511, 512, 513, 899, 900, 901, 902, 1199, 1200, 1201, 3000]
+    assert golden["fuzz_bytes"].size == sum(lens)
+    off = 0
+    for i, L in enumerate(lens):
+        d = golden["fuzz_bytes"][off:off + L].tobytes()
+        off += L
+        assert oracle.city64(d) == int(golden["fuzz_city64"][i])
+        assert oracle.citycrc128(d) == tuple(int(x) for x in golden["fuzz_crc128"][i])
+        assert oracle.city128(d) == tuple(int(x) for x in golden["fuzz_city128"][i])
+        if R is not None:
+            assert oracle.city64(d) == R.CityHash64(d, L)
+            r = R.CityHashCrc128(d, L)
+            assert oracle.citycrc128(d) == (r.first, r.second)
+            r = R.CityHash128(d, L)
+            assert oracle.city128(d) == (r.first, r.second)
 
 
 def test_cpu_bucketing_baseline_is_the_stable_bucketing(oracle):

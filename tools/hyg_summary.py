@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Measurement table from same-run files: for every config, the bench line
-(bench.json) and the rocprofv3 kernel trace of THAT run (run_kernel_trace.csv,
+(bench.json, a `bench.py --full` line: parity and the CPU baseline are read
+from it) and the rocprofv3 kernel trace of THAT run (run_kernel_trace.csv,
 tools/gpu_session.sh hyg_<cfg>).  For each config it prints
 
   * the bench line's own figures: Gkeys/s, roofline frac (algorithmic bytes
