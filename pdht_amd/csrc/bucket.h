@@ -36,6 +36,16 @@ constexpr u32 kBucketMaxRanks = 8192;  // LDS bins (32 KiB)
 constexpr u32 kBucketChunk = 32;       // tiles per colscan chunk
 constexpr u32 kStagedMaxRanks = 2048;
 
+// LDS of one workgroup: `dyn` bytes passed at launch; `fixed` = lds_fixed<S>, the kernel's __shared__ struct S
+// rounded up to the u64 dynamic array's alignment.  One constexpr function beside each kernel returns both. The
+// kernels declare each static with the type of its field of S (one object changed their code, EXPERIMENTS.md §R7).
+struct LdsBytes {
+  size_t dyn, fixed;
+  constexpr size_t total() const { return dyn + fixed; }
+};
+template <class S>
+constexpr size_t lds_fixed = (sizeof(S) + alignof(u64) - 1) / alignof(u64) * alignof(u64);
+
 __device__ __forceinline__ u64 packed_key_hash(const uint8_t *keys, u64 i, u32 L) {
   return city64(GlobalReader{keys + i * (u64)L}, (u64)L);
 }
@@ -229,7 +239,6 @@ __device__ __forceinline__ u64 same_bucket_lanes(bool valid, u32 r, u32 nbits) {
   return same;
 }
 
-
 // Exclusive scan of one value per thread over an NW-wave workgroup.
 template <int NW, class T = u32>
 __device__ __forceinline__ T block_exclusive_scan(T v, T *scratch /* NW words */) {
@@ -300,7 +309,6 @@ __global__ __launch_bounds__(kBaseThreads) void k_bucket_base(const u64 *__restr
     offsets_out[r] = tot[r];
   }
 }
-
 
 template <bool PACK>
 struct RunTab {
@@ -609,10 +617,17 @@ __device__ __forceinline__ void staged_store(u64 *stage, const u32 *delta, u32 t
 // 8-B keys, 1024 ranks.
 constexpr int kStW = 4, kStKPL = 16;
 constexpr u32 kStTile = kStW * kStKPL * 64;
-constexpr size_t kStagedStaticLds = 64;  // >= the staged kernels' static __shared__ bytes (<= 40)
-constexpr size_t staged_lds_bytes(u32 nranks, int W = kStW, int KPL = kStKPL, bool PACK = false, int OB = 0) {
-  return (size_t)W * KPL * 64 * 10 + (PACK ? (size_t)W * ((nranks + 1) & ~1u) * 2 : (size_t)W * nranks * 4) +
-         (size_t)nranks * 4 + (size_t)W * OB * nranks;
+template <int W>
+struct StagedShared {
+  u32 scan_scratch[W];
+  u32 ticket;  // the tile claimed by XcdTickets::next
+};
+// dyn: stage + sidx, the run tables, delta, the owner tables
+template <int W = kStW, int KPL = kStKPL, bool PACK = false, int OB = 0>
+constexpr LdsBytes staged_lds(u32 nranks) {
+  return {(size_t)W * KPL * 64 * 10 + (PACK ? (size_t)W * ((nranks + 1) & ~1u) * 2 : (size_t)W * nranks * 4) +
+              (size_t)nranks * 4 + (size_t)W * OB * nranks,
+          lds_fixed<StagedShared<W>>};
 }
 // Per-entry branches around the stores measured 12 % faster than clamped
 // branch-free stores (r01), although the branch-free form has no SGPR spills:
@@ -660,7 +675,7 @@ void k_bucket_scatter_staged(
   uint16_t *sidx = reinterpret_cast<uint16_t *>(stage + kTile);  // [kTile]
   const RunTab<PACK> run{reinterpret_cast<u32 *>(sidx + kTile), PACK ? (nranks + 1) & ~1u : nranks};
   u32 *delta = run.t + run.words(W);                            // [nranks]
-  __shared__ u32 scan_scratch[W];
+  __shared__ decltype(StagedShared<W>::scan_scratch) scan_scratch;
   constexpr u32 kSub = KPL * 64;
   const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // each thread owns a run of ranks for the scan (an even run when packed:
@@ -668,7 +683,8 @@ void k_bucket_scatter_staged(
   u32 per = (nranks + kB - 1) / kB;
   if (PACK) per = (per + 1) & ~1u;
   const u32 rb0 = min(threadIdx.x * per, nranks), rb1 = min(rb0 + per, nranks);
-  __shared__ u32 s_ticket;
+  __shared__ decltype(StagedShared<W>::ticket) s_ticket;
+  static_assert(sizeof(scan_scratch) + sizeof(s_ticket) == sizeof(StagedShared<W>), "every field, nothing else");
   const XcdTickets tk(tickets, ntiles);
   TileOrder o(ntiles);
   if constexpr (DYN) o.t = tk.next(&s_ticket), o.end = tk.hi;
@@ -828,12 +844,15 @@ struct TwoPassTL {
   }
 };
 
+template <int W>
+struct TlPass1Shared {
+  u32 runt[W * kTpMaxDigits];
+  u32 scan_scratch[W];
+};
 template <int W, int KPL>
-constexpr size_t tl_pass1_lds_bytes(u32 nranks) {
-  return (size_t)W * KPL * 64 * (8 + 2) + (size_t)((nranks + 1) / 2) * 4;
+constexpr LdsBytes tl_pass1_lds(u32 nranks) {
+  return {(size_t)W * KPL * 64 * (8 + 2) + (size_t)((nranks + 1) / 2) * 4, lds_fixed<TlPass1Shared<W>>};
 }
-template <int W, int KPL>
-constexpr size_t tl_pass2_lds_bytes() { return (size_t)W * KPL * 64 * (8 + 4); }
 
 template <int L, int W, int KPL, int WPE, bool NTK = true>
 __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(WPE)))
@@ -844,8 +863,10 @@ void k_bucket_tl_pass1(const uint8_t *__restrict__ keys, FastMod rk, u32 nranks,
   u64 *stage = lds64;                                            // [kTile] key pieces in f order
   uint16_t *sidx = reinterpret_cast<uint16_t *>(stage + kTile);  // [kTile] tile-local index in f order
   u32 *hist = reinterpret_cast<u32 *>(sidx + kTile);            // [(nranks+1)/2] u16 pairs: the chunk's ranks
-  __shared__ u32 runt[W * kTpMaxDigits];
-  __shared__ u32 scan_scratch[W];
+  __shared__ decltype(TlPass1Shared<W>::runt) runt;  // (typed by the struct's fields, as in the staged scatter)
+  __shared__ decltype(TlPass1Shared<W>::scan_scratch) scan_scratch;
+  static_assert(sizeof(runt) + sizeof(scan_scratch) == sizeof(TlPass1Shared<W>), "every field, nothing else");
+  static_assert(W * 64 >= kTpMaxDigits, "one thread per fine bucket");
   const RunTab<false> run{runt, tp.F};
   const u32 fmask = tp.F - 1;
   const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -931,6 +952,21 @@ void k_bucket_tl_pass1(const uint8_t *__restrict__ keys, FastMod rk, u32 nranks,
   }
 }
 
+template <int W>
+struct TlPass2Shared {
+  u32 runt[W * kTpMaxDigits];
+  u32 delta[kTpMaxDigits];
+  u32 running[kTpMaxDigits];       // next final slot of bucket c*F + f
+  u32 tcount[kTpMaxDigits];
+  u32 bpre[kBucketMaxRanks / 64];  // first final slot of each block of 64 ranks
+  u32 scan_scratch[W];
+  u32 len;                         // keys of the segment
+};
+template <int W, int KPL>
+constexpr LdsBytes tl_pass2_lds() {
+  return {(size_t)W * KPL * 64 * (8 + 4), lds_fixed<TlPass2Shared<W>>};
+}
+
 // PROBE (A/B timing only, wrong outputs): 1 = every sub-tile reads its rows
 // contiguously from row o.t * 3840 instead of through the row map (what the
 // gather costs).
@@ -949,14 +985,18 @@ void k_bucket_tl_pass2(FastMod rk, u32 nranks, TwoPassTL tp, Out out) {
   extern __shared__ u64 lds64[];
   u64 *stage = lds64;                                  // [kTile] digests / key pieces
   u32 *sidx = reinterpret_cast<u32 *>(stage + kTile);  // [kTile] source rows of the sub-tile, then original indices
-  __shared__ u32 runt[W * kTpMaxDigits];
-  __shared__ u32 running[kTpMaxDigits];  // next final slot of bucket c*F + f
-  __shared__ u32 delta[kTpMaxDigits];
-  __shared__ u32 tcount[kTpMaxDigits];
-  __shared__ u32 scan_scratch[W];
-  __shared__ u32 s_len;
-  __shared__ u32 bpre[kBucketMaxRanks / 64];  // first final slot of each block of 64 ranks
+  using Sh = TlPass2Shared<W>;
+  __shared__ decltype(Sh::runt) runt;
+  __shared__ decltype(Sh::running) running;
+  __shared__ decltype(Sh::delta) delta;
+  __shared__ decltype(Sh::tcount) tcount;
+  __shared__ decltype(Sh::scan_scratch) scan_scratch;
+  __shared__ decltype(Sh::len) s_len;
+  __shared__ decltype(Sh::bpre) bpre;
+  static_assert(sizeof(runt) + sizeof(running) + sizeof(delta) + sizeof(tcount) + sizeof(scan_scratch) +
+                    sizeof(s_len) + sizeof(bpre) == sizeof(Sh), "every field of TlPass2Shared, and nothing else");
   static_assert(kBucketMaxRanks / 64 <= kB, "one thread per 64-rank block");
+  static_assert(W * 64 >= kTpMaxDigits, "one thread per coarse bucket");
   {
     const u32 nblk = (nranks + 63) / 64;
     const u32 v = threadIdx.x < nblk ? tp.bsum[threadIdx.x] : 0u;

@@ -130,10 +130,15 @@ __global__ __launch_bounds__(64 * kCsWaves) void k_bucket_chunkscan2(u32 *__rest
 // r02-r03 shape of both passes (4 waves x 8 keys per lane, 4 WG/CU); since r04
 // pass 1 runs 8 x 8 @ 2 and 16-B keys' pass 2 too (launch_two_pass_sel).
 constexpr int kTpW = 4, kTpKPL = 8, kTpPerCu = 4;
+// (fixed: the kernels' loose statics below, rounded up to 8 B -- runt,
+// running, delta, tcount, scan_scratch, and pass 2's seg[2])
+constexpr size_t r05_fixed_lds(int W, int more) {
+  return (((size_t)W * kTpMaxDigits + 3 * kTpMaxDigits + W + more) * 4 + 7) & ~(size_t)7;
+}
 template <int W, int KPL>
-constexpr size_t pass1_lds_bytes() { return (size_t)W * KPL * 64 * (8 + 2 + 1); }
+constexpr LdsBytes pass1_lds() { return {(size_t)W * KPL * 64 * (8 + 2 + 1), r05_fixed_lds(W, 0)}; }
 template <int W, int KPL>
-constexpr size_t pass2_lds_bytes() { return (size_t)W * KPL * 64 * (8 + 4); }
+constexpr LdsBytes pass2_lds() { return {(size_t)W * KPL * 64 * (8 + 4), r05_fixed_lds(W, 2)}; }
 
 template <int L, int W = kTpW, int KPL = kTpKPL, int WPE = 8>
 __global__ __launch_bounds__(W * 64) __attribute__((amdgpu_waves_per_eu(WPE)))
@@ -329,22 +334,21 @@ void k_bucket_pass2(FastMod rk, u32 nranks, TwoPass tp, Out out) {
 template <int L, class Out, int W = kTpW, int KPL = kTpKPL, int PER_CU = kTpPerCu, int W1 = W, int KPL1 = KPL,
           int PER_CU1 = PER_CU, bool ONE = (L == 8 && !Out::kPair8)>
 static int launch_two_pass(const BucketArgs &a, const TwoPass &tp, const Out &out, hipStream_t st, int dev) {
-  static const char *const names[3] = {"k_bucket_pass2<8B>", "k_bucket_pass2<16B>", "k_bucket_pass2<32B>"};
   constexpr int WPE = PER_CU * W / 4 > 8 ? 8 : PER_CU * W / 4;      // waves per SIMD, pass 2
   constexpr int WPE1 = PER_CU1 * W1 / 4 > 8 ? 8 : PER_CU1 * W1 / 4;  // pass 1
-  const size_t b1 = pass1_lds_bytes<W1, KPL1>(), b2 = pass2_lds_bytes<W, KPL>();
-  auto f1 = &k_bucket_pass1<L, W1, KPL1, WPE1>;
-  auto f2 = &k_bucket_pass2<L, Out, W, KPL, WPE, ONE>;
-  if (int rc = set_lds(reinterpret_cast<const void *>(f1), b1)) return rc;
-  if (int rc = set_lds(reinterpret_cast<const void *>(f2), b2)) return rc;
+  const LdsBytes b1 = pass1_lds<W1, KPL1>(), b2 = pass2_lds<W, KPL>();
+  constexpr auto f1 = &k_bucket_pass1<L, W1, KPL1, WPE1>;
+  constexpr auto f2 = &k_bucket_pass2<L, Out, W, KPL, WPE, ONE>;
+  if (int rc = set_lds<f1>(b1)) return rc;
+  if (int rc = set_lds<f2>(b2)) return rc;
   const u64 cus = (u64)std::max(1, g_dev[dev].cus);
   unsigned g1 = (unsigned)std::min<u64>(a.ntiles, cus * PER_CU1);
   if (g1 >= 8) g1 &= ~7u;  // XCD-contiguous tile order (TileOrder)
-  f1<<<g1, W1 * 64, b1, st>>>(a.k, a.n, a.rk, tp);
+  f1<<<g1, W1 * 64, b1.dyn, st>>>(a.k, a.n, a.rk, tp);
   unsigned g2 = (unsigned)std::min<u64>(tp.nseg, cus * PER_CU);
   if (g2 >= 8) g2 &= ~7u;
-  f2<<<g2, W * 64, b2, st>>>(a.rk, a.nranks, tp, out);
-  g_kernel = names[L == 8 ? 0 : L == 16 ? 1 : 2];
+  f2<<<g2, W * 64, b2.dyn, st>>>(a.rk, a.nranks, tp, out);
+  g_kernel = PDHT_KEY_TAG(L, "k_bucket_pass2", "");
   return 0;
 }
 
@@ -502,15 +506,11 @@ static int bucket_r05(const BucketArgs &a0, const BucketWs &w, size_t keysize, c
     const u64 nfchunks = (ntiles + tp.fchunk - 1) / tp.fchunk;
     u32 *cF = fscan ? r.chunksF : nullptr;
     const unsigned gc = (unsigned)std::min<u64>(tp.nchunks, (u64)std::max(1, g_dev[dev].cus) * 8);
-    if (keysize == 8)
-      k_bucket_count_tp<8><<<gc, kBlock, hist_lds, st>>>(a.k, n, a.rk, nranks, tp.F, r.countsF, r.chunkcnt,
-                                                          ntiles, cF);
-    else if (keysize == 16)
-      k_bucket_count_tp<16><<<gc, kBlock, hist_lds, st>>>(a.k, n, a.rk, nranks, tp.F, r.countsF, r.chunkcnt,
-                                                           ntiles, cF);
-    else
-      k_bucket_count_tp<32><<<gc, kBlock, hist_lds, st>>>(a.k, n, a.rk, nranks, tp.F, r.countsF, r.chunkcnt,
-                                                           ntiles, cF);
+    with_keysize(keysize, [&](auto L) {
+      k_bucket_count_tp<L>
+          <<<gc, kBlock, hist_lds, st>>>(a.k, n, a.rk, nranks, tp.F, r.countsF, r.chunkcnt, ntiles, cF);
+      return 0;
+    });
     if (!fscan)
       k_bucket_colscan<<<dim3((tp.F + 63) / 64, (unsigned)nfchunks), 64, 0, st>>>(r.countsF, ntiles, tp.F,
                                                                                    r.chunksF);
@@ -524,9 +524,7 @@ static int bucket_r05(const BucketArgs &a0, const BucketWs &w, size_t keysize, c
   g_kernel = "k_bucket_base";
   if (!ntiles) return 0;
   k_bucket_fbase<<<1, kTpMaxDigits, 0, st>>>(r.totalsF, tp.F, r.fbase);
-  return keysize == 8    ? launch_two_pass_sel<8, Out>(a, tp, out, st, dev)
-         : keysize == 16 ? launch_two_pass_sel<16, Out>(a, tp, out, st, dev)
-                         : launch_two_pass_sel<32, Out>(a, tp, out, st, dev);
+  return with_keysize(keysize, [&](auto L) { return launch_two_pass_sel<L, Out>(a, tp, out, st, dev); });
 }
 
 // The hooks pdht_bucket.hip calls: the r02-r05 form under its variants, and

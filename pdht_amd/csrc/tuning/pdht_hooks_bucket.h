@@ -60,20 +60,13 @@ static int hook_tl_shape(const BucketArgs &a, const TwoPassTL &tl, const Out &ou
   const int v = tuning_variant();
   if constexpr (L <= 16) {
     constexpr int K1 = L == 8 ? 8 : 4;  // pass-1 keys per lane at the product's tile
-    if constexpr (L == 16)
-      if (v == 302) {  // pass 1 in 8 x 8 (4096-key tiles, hook_tl_tile_shift), pass 2 as 304
-        if constexpr (Out::kPair8)
-          return launch_tl<L, Out, 4, 4, 4, 8, 8, 2>(a, tl, out, w, bucket_offsets, st, dev);
-        else
-          return launch_tl<L, Out, 8, 8, 2, 8, 8, 2>(a, tl, out, w, bucket_offsets, st, dev);
-      }
-    if constexpr (L == 16)
-      if (v == 304) {  // 16-B keys' pass 2 before r06's last shape change: arrays 8 x 8 @ 2, records 4 x 4 @ 4
-        if constexpr (Out::kPair8)
-          return launch_tl<L, Out, 4, 4, 4, 8, 4, 2>(a, tl, out, w, bucket_offsets, st, dev);
-        else
-          return launch_tl<L, Out, 8, 8, 2, 8, 4, 2>(a, tl, out, w, bucket_offsets, st, dev);
-      }
+    if constexpr (L == 16) {
+      // 304: 16-B keys' pass 2 before r06's last shape change (arrays 8 x 8 @ 2, records 4 x 4 @ 4);
+      // 302: with pass 1 in 8 x 8 (4096-key tiles, hook_tl_tile_shift)
+      constexpr int W2 = Out::kPair8 ? 4 : 8, KPL2 = Out::kPair8 ? 4 : 8, PER_CU2 = Out::kPair8 ? 4 : 2;
+      if (v == 302) return launch_tl<L, Out, W2, KPL2, PER_CU2, 8, 8, 2>(a, tl, out, w, bucket_offsets, st, dev);
+      if (v == 304) return launch_tl<L, Out, W2, KPL2, PER_CU2, 8, 4, 2>(a, tl, out, w, bucket_offsets, st, dev);
+    }
     if (v == 298)  // timing probe: pass 2 reading contiguous rows (wrong outputs)
       return launch_tl<L, Out, 8, 8, 2, 8, K1, 2, 1>(a, tl, out, w, bucket_offsets, st, dev);
     if (v == 291) return launch_tl<L, Out, 4, 8, 4, 8, K1, 2>(a, tl, out, w, bucket_offsets, st, dev);
@@ -82,27 +75,11 @@ static int hook_tl_shape(const BucketArgs &a, const TwoPassTL &tl, const Out &ou
     if (v == 294 || v == 295 || v == 297)
       return launch_tl<L, Out, 8, 8, 2, 16, 8, 1>(a, tl, out, w, bucket_offsets, st, dev);
   }
-  if (v == 320) {  // the product's shapes, pass 2 gathering with non-temporal loads (r06 before the switch)
-    if constexpr (L == 8 && !Out::kPair8)
-      return launch_tl<L, Out, 8, 8, 2, 8, 8, 2, 0, true>(a, tl, out, w, bucket_offsets, st, dev);
-    else if constexpr (L == 8)
-      return launch_tl<L, Out, 8, 4, 2, 8, 8, 2, 0, true>(a, tl, out, w, bucket_offsets, st, dev);
-    else if constexpr (L == 32 && Out::kPair8)
-      return launch_tl<L, Out, 4, 4, 4, 8, 4, 2, 0, false>(a, tl, out, w, bucket_offsets, st, dev);
-    else
-      return launch_tl<L, Out, 8, 4, 2, 8, 4, 2, 0, true>(a, tl, out, w, bucket_offsets, st, dev);
-  }
-  if (v == 322) {  // the product's shapes, pass 1 loading its keys with plain (temporal) loads
-    constexpr bool NG = L == 32 && Out::kPair8;
-    if constexpr (L == 8 && !Out::kPair8)
-      return launch_tl<L, Out, 8, 8, 2, 8, 8, 2, 0, NG, false>(a, tl, out, w, bucket_offsets, st, dev);
-    else if constexpr (L == 8)
-      return launch_tl<L, Out, 8, 4, 2, 8, 8, 2, 0, NG, false>(a, tl, out, w, bucket_offsets, st, dev);
-    else if constexpr (L == 32 && Out::kPair8)
-      return launch_tl<L, Out, 4, 4, 4, 8, 4, 2, 0, NG, false>(a, tl, out, w, bucket_offsets, st, dev);
-    else
-      return launch_tl<L, Out, 8, 4, 2, 8, 4, 2, 0, NG, false>(a, tl, out, w, bucket_offsets, st, dev);
-  }
+  constexpr bool NG = L == 32 && Out::kPair8;  // the product's gather policy
+  if (v == 320)  // the product's shapes, pass 2 gathering with non-temporal loads (r06 before the switch)
+    return launch_tl_product<L, Out, !NG>(a, tl, out, w, bucket_offsets, st, dev);
+  if (v == 322)  // the product's shapes, pass 1 loading its keys with plain (temporal) loads
+    return launch_tl_product<L, Out, NG, false>(a, tl, out, w, bucket_offsets, st, dev);
   if constexpr (L == 8 && !Out::kPair8)
     if (v == 323)  // 8-B arrays' pass 2 storing in two phases (metadata, then the keys)
       return launch_tl<L, Out, 8, 8, 2, 8, 8, 2, 0, false, true, false>(a, tl, out, w, bucket_offsets, st, dev);
@@ -114,28 +91,14 @@ static int hook_tl_shape(const BucketArgs &a, const TwoPassTL &tl, const Out &ou
 
 // 85: the staged scatter in the static tile order (the r02 default before the
 // per-XCD tickets)
-template <class Out, class S>
+template <class Out>
 static int hook_staged_launch(bool staged, size_t keysize, const BucketArgs &a, const Out &out, hipStream_t st,
-                              int dev, S shape, u32 *tickets) {
+                              int dev, StagedShape shape, u32 *tickets) {
   if (!staged) return kNoVariant;
   const int v = tuning_variant();
-  if (v == 85)
-    return keysize == 8    ? launch_staged<8, Out>(a, out, st, dev)
-           : keysize == 16 ? launch_staged<16, Out>(a, out, st, dev)
-                           : launch_staged<32, Out>(a, out, st, dev);
-  if (v == 321) {  // the product's shapes, keys loaded non-temporally (r02-r06 before the switch)
-    if (shape == S::kOwner8x16)
-      return keysize == 8    ? launch_staged<8, Out, false, 8, 16, true, 2, true>(a, out, st, dev, tickets)
-             : keysize == 16 ? launch_staged<16, Out, false, 8, 16, true, 2, true>(a, out, st, dev, tickets)
-                             : launch_staged<32, Out, false, 8, 16, true, 2, true>(a, out, st, dev, tickets);
-    if (shape == S::kOwner4x16)
-      return keysize == 8    ? launch_staged<8, Out, false, kStW, kStKPL, true, 2, true>(a, out, st, dev, tickets)
-             : keysize == 16 ? launch_staged<16, Out, false, kStW, kStKPL, true, 2, true>(a, out, st, dev, tickets)
-                             : launch_staged<32, Out, false, kStW, kStKPL, true, 2, true>(a, out, st, dev, tickets);
-    return keysize == 8    ? launch_staged<8, Out, false, kStW, kStKPL, true, 0, true>(a, out, st, dev, tickets)
-           : keysize == 16 ? launch_staged<16, Out, false, kStW, kStKPL, true, 0, true>(a, out, st, dev, tickets)
-                           : launch_staged<32, Out, false, kStW, kStKPL, true, 0, true>(a, out, st, dev, tickets);
-  }
+  if (v == 85) return with_keysize(keysize, [&](auto L) { return launch_staged<L, Out>(a, out, st, dev); });
+  // 321: the product's shapes, keys loaded non-temporally (r02-r06 before the switch)
+  if (v == 321) return launch_staged_shape<Out, true>(shape, keysize, a, out, st, dev, tickets);
   return kNoVariant;
 }
 

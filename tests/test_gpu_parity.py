@@ -629,15 +629,16 @@ def _bucket_kernel(L, nranks, variant, records=False):
             return f"k_bucket_pass2<{L}B>" if r05 else f"k_bucket_tl_pass2<{L}B>"
         # staged_shape(): owner-table ranking for array outputs from 512
         # ranks, on 8 x 16 tiles for 8/16-B keys while 81920 + 52 B per rank
-        # of LDS fits a CU, else on 4 x 16 tiles while 40960 + 28 B per rank
-        # leaves two workgroups per CU; ballots otherwise
+        # of dynamic LDS and the kernel's 40 fixed bytes fit a CU, else on
+        # 4 x 16 tiles while 40960 + 28 B per rank stay within 80 KiB;
+        # ballots otherwise
         if variant == 83:
             return f"k_bucket_scatter_staged<{L}B,own,8x16>"
         if variant == 87:
             return f"k_bucket_scatter_staged<{L}B,own>"
         if variant in (85, 89) or records or nranks < 512:
             return f"k_bucket_scatter_staged<{L}B>"
-        if L != 32 and 81920 + 52 * nranks + 64 <= 160 * 1024:
+        if L != 32 and 81920 + 52 * nranks + 40 <= 160 * 1024:
             return f"k_bucket_scatter_staged<{L}B,own,8x16>"
         if 40960 + 28 * nranks <= 80 * 1024:
             return f"k_bucket_scatter_staged<{L}B,own>"
@@ -763,6 +764,33 @@ def test_bucket_records(dev, oracle, L, nranks, n, variant):
     assert (R[:, 24 + L:] == 0).all()
     ty, sr, hi, ix, mb, ko = P.record_fields(rec, L)
     assert (u64(mb) == m2[order]).all() and (ix.cpu().numpy().view(np.uint32) == order).all()
+
+
+def test_bucket_records_needs_the_records_workspace(dev):
+    """Arrays and records take two passes from different rank counts, so each
+    has its own workspace query (ABI 4).  32-B keys at 1024
+    ranks: records take two passes, arrays do not, and the arrays' size is
+    too small for pdht_bucket_records_dev -- refused before any launch, by
+    the C ABI and by the wrapper; the records' size works."""
+    n, L, nranks = 4097, 32, 1024
+    small = P.bucket_workspace_bytes(n, L, nranks)
+    need = P.bucket_workspace_bytes(n, L, nranks, records=True)
+    assert small < need
+    k = torch.randint(0, 256, (n, L), dtype=torch.uint8, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    rec = torch.empty(n * P.bucket_record_bytes(L) // 8, dtype=torch.int64, device=dev)
+    offs = torch.zeros(nranks + 1, dtype=torch.int64, device=dev)
+    lib = P.lib()
+    s = torch.cuda.current_stream(dev).cuda_stream
+    assert lib.pdht_bucket_records_dev(k.data_ptr(), L, n, nranks, P.PDHT_PUT, 0, 0, ws.data_ptr(), small,
+                                       rec.data_ptr(), offs.data_ptr(), s) != 0
+    assert b"workspace too small" in lib.pdht_hip_last_error()
+    with pytest.raises(ValueError, match="workspace"):
+        P.bucket_records(k, nranks, workspace=ws[:small])
+    _, offs = P.bucket_records(k, nranks, workspace=ws)
+    assert P.last_kernel() == "k_bucket_tl_pass2<32B>"
+    o = offs.cpu().numpy()
+    assert o[0] == 0 and o[-1] == n and (np.diff(o) >= 0).all()
 
 
 @pytest.mark.parametrize("nranks,shard", [(1, 0), (2, 1), (4, 3), (8, 7), (1024, 0), (8192, 5)])
