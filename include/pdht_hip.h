@@ -210,4 +210,9 @@ int pdht_hip_key_stream_var_dev(const void *bytes, size_t nbytes, const uint64_t
 #ifdef __cplusplus
 }
 #endif
+
+/* Put records with values and row gather / scatter in bucket order: same ABI,
+ * same libraries, declared (with the record layout) in a header of their own. */
+#include "pdht_hip_put.h"
+
 #endif /* PDHT_HIP_H_ */

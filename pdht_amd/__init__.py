@@ -116,6 +116,11 @@ def _declare(L, tuning=False):
         "pdht_bucket_batch_dev": (C.c_int, [_V, _S, _S, _U32, _U32, _V, _S, _V, _V, _V, _V, _V, _V]),
         "pdht_bucket_record_bytes": (C.c_size_t, [_S]),
         "pdht_bucket_records_dev": (C.c_int, [_V, _S, _S, _U32, _U32, _U32, _U32, _V, _S, _V, _V, _V]),
+        "pdht_bucket_put_record_bytes": (C.c_size_t, [_S, _S, _S]),
+        "pdht_bucket_put_records_dev": (C.c_int, [_V, _S, _V, _S, _S, _S, _U32, _U32, _U32, _U32, _S, _V, _S, _V,
+                                                  _V, _V]),
+        "pdht_gather_rows_dev": (C.c_int, [_V, _S, _S, _V, _S, _S, _V, _S, _V]),
+        "pdht_scatter_rows_dev": (C.c_int, [_V, _S, _S, _V, _S, _S, _V, _S, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
         "CityHash64WithSeeds": (_U64, [_V, _S, _U64, _U64]),
@@ -701,6 +706,156 @@ def record_fields(records, keysize: int):
     w32 = flat.view(torch.int32).view(m, rb // 4)
     w64 = flat.view(torch.int64).view(m, rb // 8)
     return w32[:, 0], w32[:, 1], w32[:, 2], w32[:, 3], w64[:, 2], records[:, 24:24 + keysize]
+
+
+# ------------------------------------------- put records and row movers ---
+# The payload half of bucketing (include/pdht_hip_put.h).
+#   put: bucket_put_records(keys, values, nranks) -> dist.exchange_records
+#        (the stride is records.shape[1]) -> put_record_fields on the receiver;
+#   get: the replies come back in bucket order (reply p answers record p);
+#        scatter_rows(replies, index) puts reply p at row index[p], the
+#        caller's order, index being record_fields(records, L)[3] or
+#        bucket_batch's index output.  gather_rows(rows, index) is the
+#        inverse: rows into bucket order.
+def put_record_bytes(keysize: int, elemsize: int, key_slot: int = 0) -> int:
+    """Stride of a put record: 24 + slot + elemsize rounded up to 8, slot =
+    key_slot or keysize rounded up to 8.  key_slot must be 0 or a multiple of
+    8 that is >= keysize (32 = PDHT_MAXKEYSIZE gives putget.c's sbuf)."""
+    rb = lib().pdht_bucket_put_record_bytes(keysize, key_slot, elemsize)
+    if rb == 0:
+        raise ValueError(f"key_slot {key_slot} must be 0 or a multiple of 8 that is >= keysize {keysize}")
+    return rb
+
+
+def _rows_2d(t, name, device=None):
+    """t: uint8 CUDA tensor [m, rowbytes] with unit inner stride; rows may be
+    strided (a column slice of a wider tensor) and start at any address."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda:
+        raise ValueError(f"{name} must be a CUDA uint8 tensor of shape [rows, rowbytes]")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} must be on {device}")
+    m, B = t.shape
+    if B == 0:
+        raise ValueError(f"{name} must have at least one byte per row")
+    if m and B > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} rows must be contiguous")
+    stride = t.stride(0) if m > 1 else B
+    if stride < B:
+        raise ValueError(f"{name} rows overlap (row stride {stride} < {B} bytes)")
+    return m, B, stride
+
+
+def bucket_put_records(keys, values, nranks: int, *, key_slot: int = 0, msg_type: int = PDHT_PUT,
+                       src_rank: int = 0, ht_index: int = 0, stream=None, out=None, workspace=None):
+    """Destination bucketing into put records (include/pdht_hip_put.h
+    pdht_bucket_put_records_dev): bucket_records' header + key, padded to the
+    key slot, + the key's value -- bucket r = records[offsets[r]:offsets[r+1]]
+    is the send buffer of a put batch for rank r.
+
+    keys [n, L] packed uint8; values [n, E] uint8, row i the value of key i (a
+    column slice of a wider tensor is accepted: its row stride is passed on).
+    Returns (records uint8 [n, put_record_bytes(L, E, key_slot)], offsets int64
+    [nranks+1]); put_record_fields() splits them.  `out` = a previous return
+    value to reuse; `workspace` as for bucket_records
+    (bucket_workspace_bytes(n, L, nranks, records=True) bytes).
+
+    Put flow: bucket_put_records -> dist.exchange_records -> put_record_fields.
+    Get flow: the replies return in bucket order -> scatter_rows(replies, index).
+    """
+    torch = _torch()
+    n, L, stride = _keys_2d(keys)
+    if stride != L:
+        raise ValueError("bucket_put_records needs packed keys")
+    dev = keys.device
+    nv, E, vstride = _rows_2d(values, "values", dev)
+    if nv != n:
+        raise ValueError(f"values must have one row per key: {nv} rows for {n} keys")
+    rb = put_record_bytes(L, E, key_slot)
+    ws, ws_bytes = _workspace(workspace, n, L, nranks, dev, records=True)
+    if out is not None:
+        rec, offs = out
+        _need(rec, "out[0] (records)", torch.uint8, dev, shape=(n, rb))
+        if rec.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned")
+        _need(offs, "out[1] (offsets)", torch.int64, dev, shape=(nranks + 1,))
+    else:
+        # int64 storage keeps the records 8-byte aligned
+        rec = torch.empty(max(n * rb // 8, 1), dtype=torch.int64, device=dev).view(torch.uint8)[: n * rb]
+        rec = rec.view(n, rb)
+        offs = torch.empty(nranks + 1, dtype=torch.int64, device=dev)
+    with _on(dev, stream) as g:
+        _check(lib().pdht_bucket_put_records_dev(_dptr(keys), L, _dptr(values), E, vstride, n, nranks, msg_type,
+                                                 src_rank, ht_index, key_slot, _dptr(ws), ws_bytes, _dptr(rec),
+                                                 _dptr(offs), g.stream),
+               "pdht_bucket_put_records_dev")
+    return rec, offs
+
+
+def put_record_fields(records, keysize: int, elemsize: int, key_slot: int = 0):
+    """Views of a put-record batch [m, stride] (uint8): record_fields' tuple
+    plus values uint8 [m, elemsize]."""
+    rb = put_record_bytes(keysize, elemsize, key_slot)
+    if records.dim() != 2 or records.shape[1] != rb:
+        raise ValueError(f"records must have shape [m, {rb}], got {tuple(records.shape)}")
+    slot = key_slot if key_slot else (keysize + 7) // 8 * 8
+    return record_fields(records, keysize) + (records[:, 24 + slot:24 + slot + elemsize],)
+
+
+def _move_rows(src, index, out, stream, check, scatter):
+    torch = _torch()
+    name = "scatter_rows" if scatter else "gather_rows"
+    rows, B, sstride = _rows_2d(src, "src")
+    dev = src.device
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or \
+            not index.is_cuda or index.device != dev:
+        raise ValueError(f"index must be a 1-D int32 tensor on {dev}")
+    m = index.numel()
+    istride = 4 * index.stride(0) if m > 1 else 4
+    if istride < 4:
+        raise ValueError("index must have a positive stride")
+    if scatter and rows != m:
+        raise ValueError(f"scatter_rows: src has {rows} rows, index {m} entries")
+    if out is None:
+        out = torch.empty((m, B), dtype=torch.uint8, device=dev)
+    orows, oB, ostride = _rows_2d(out, "out", dev)
+    if oB != B or (not scatter and orows != m):
+        raise ValueError(f"out must have shape [{'rows' if scatter else m}, {B}], got {tuple(out.shape)}")
+    limit = orows if scatter else rows
+    if check and m:
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            if not torch.cuda.is_current_stream_capturing():
+                top = int((index.to(torch.int64) & 0xFFFFFFFF).max().item())
+                if top >= limit:
+                    raise ValueError(f"{name}: index {top} is past the {limit} rows it indexes")
+    with _on(dev, stream) as g:
+        f = lib().pdht_scatter_rows_dev if scatter else lib().pdht_gather_rows_dev
+        _check(f(_dptr(src), sstride, B, _dptr(index), istride, m, _dptr(out), ostride, g.stream),
+               f"pdht_{name}_dev")
+    return out
+
+
+def gather_rows(src, index, out=None, stream=None, check=True):
+    """out[p] = src[index[p]] (include/pdht_hip_put.h pdht_gather_rows_dev): rows
+    into bucket order.  src uint8 [rows, B]; index int32 [m] (unsigned row
+    numbers, as bucket_batch returns them; a strided view such as
+    record_fields(...)[3] is read in place; repeats allowed); out uint8 [m, B]
+    (allocated if None).  src and out may be row-strided views at any
+    address; bytes of out outside its rows are not written.  check=True reads
+    the largest index back on the launch stream (host-synchronous) and
+    raises if it is past src's rows; check=False, or during graph capture:
+    asynchronous, the caller vouches for the indices."""
+    return _move_rows(src, index, out, stream, check, False)
+
+
+def scatter_rows(src, index, out=None, stream=None, check=True):
+    """out[index[p]] = src[p] (pdht_scatter_rows_dev): rows that arrived in
+    bucket order -- get replies -- back into the caller's order.  The indices
+    must be distinct.  src uint8 [m, B]; index int32 [m]; out uint8 [rows, B]
+    (None: [m, B], index a permutation).  Rows of out that no index names keep
+    their bytes.  check as for gather_rows, against out's rows."""
+    return _move_rows(src, index, out, stream, check, True)
 
 
 def splitmix64_fill(seed: int, first: int, nwords: int, out=None, device="cuda", stream=None):

@@ -1,6 +1,8 @@
 // pdht_bucket.hip -- destination bucketing (include/pdht_hip.h
-// pdht_bucket_batch_dev / pdht_bucket_records_dev; kernels in bucket.h).
+// pdht_bucket_batch_dev / pdht_bucket_records_dev, include/pdht_hip_put.h
+// pdht_bucket_put_records_dev; kernels in bucket.h, the value mover in rows.h).
 #include "bucket.h"
+#include "rows.h"
 #include "runtime.h"
 
 // ------------------------------------------------- destination bucketing ---
@@ -464,18 +466,67 @@ PDHT_API int pdht_bucket_batch_dev(const void *keys, size_t keysize, size_t n, u
 
 PDHT_API size_t pdht_bucket_record_bytes(size_t keysize) { return 24 + ((keysize + 7) & ~(size_t)7); }
 
+// Header, index, mbits and key of every record, `stride` bytes apart (the kernels write nothing past the key,
+// except the generic-length one, which zero-fills up to the stride: OutRecT::key_copy)
+static int bucket_records_impl(const void *keys, size_t keysize, size_t n, uint32_t nranks, uint32_t msg_type,
+                               uint32_t src_rank, uint32_t ht_index, void *workspace, size_t workspace_bytes,
+                               void *records, size_t stride, uint64_t *bucket_offsets, hipStream_t st) {
+  if (n && !records) return fail("records must not be NULL%s", "");
+  if ((uintptr_t)records & 7) return fail("records must be 8-byte aligned%s", "");
+  const OutRec out{static_cast<uint8_t *>(records), (u64)stride, (u64)msg_type | ((u64)src_rank << 32), ht_index,
+                   (u32)keysize};
+  if (int rc = hook_records(out, [&](const auto &o2) {
+        return bucket_impl(keys, keysize, n, nranks, workspace, workspace_bytes, o2, 0, bucket_offsets, st);
+      });
+      rc != kNoVariant)
+    return rc;
+  return bucket_impl(keys, keysize, n, nranks, workspace, workspace_bytes, out, 0, bucket_offsets, st);
+}
+
 PDHT_API int pdht_bucket_records_dev(const void *keys, size_t keysize, size_t n, uint32_t nranks,
                                      uint32_t msg_type, uint32_t src_rank, uint32_t ht_index,
                                      void *workspace, size_t workspace_bytes, void *records,
                                      uint64_t *bucket_offsets, pdht_hip_stream_t s) {
+  return bucket_records_impl(keys, keysize, n, nranks, msg_type, src_rank, ht_index, workspace, workspace_bytes,
+                             records, pdht_bucket_record_bytes(keysize), bucket_offsets, ST(s));
+}
+
+// Put records (include/pdht_hip_put.h): the bucketing kernels write header, index, mbits and key into records of
+// the put stride; the row mover (rows.h) then reads each record's source index at +12 and writes, as one run
+// per record from the end of the key, the zeros of the key-slot gap, value[index] and its zero pad to 8.
+PDHT_API size_t pdht_bucket_put_record_bytes(size_t keysize, size_t key_slot, size_t elemsize) {
+  if (key_slot && (key_slot < keysize || (key_slot & 7))) return 0;
+  const size_t slot = key_slot ? key_slot : (keysize + 7) & ~(size_t)7;
+  return 24 + slot + ((elemsize + 7) & ~(size_t)7);
+}
+
+PDHT_API int pdht_bucket_put_records_dev(const void *keys, size_t keysize, const void *values, size_t elemsize,
+                                         size_t value_stride, size_t n, uint32_t nranks, uint32_t msg_type,
+                                         uint32_t src_rank, uint32_t ht_index, size_t key_slot, void *workspace,
+                                         size_t workspace_bytes, void *records, uint64_t *bucket_offsets,
+                                         pdht_hip_stream_t s) {
+  if (elemsize == 0) return fail("put records: elemsize must be >= 1%s", "");
+  if (n && !values) return fail("put records: values must not be NULL%s", "");
+  if (value_stride < elemsize) return fail("put records: value_stride must be >= elemsize%s", "");
+  const size_t stride = pdht_bucket_put_record_bytes(keysize, key_slot, elemsize);
+  if (stride == 0) return fail("put records: key_slot must be 0 or a multiple of 8 that is >= keysize%s", "");
+  const size_t key_end = 24 + ((keysize + 7) & ~(size_t)7), pad8 = ((elemsize + 7) & ~(size_t)7) - elemsize;
+  const RowsCall fill{values,
+                      value_stride,
+                      elemsize,
+                      static_cast<uint8_t *>(records) + 12,
+                      stride,
+                      n,
+                      static_cast<uint8_t *>(records) + key_end,
+                      stride,
+                      stride - key_end - elemsize - pad8,
+                      pad8,
+                      false};
   if (n && !records) return fail("records must not be NULL%s", "");
   if ((uintptr_t)records & 7) return fail("records must be 8-byte aligned%s", "");
-  const OutRec out{static_cast<uint8_t *>(records), (u64)pdht_bucket_record_bytes(keysize),
-                   (u64)msg_type | ((u64)src_rank << 32), ht_index, (u32)keysize};
-  if (int rc = hook_records(out, [&](const auto &o2) {
-        return bucket_impl(keys, keysize, n, nranks, workspace, workspace_bytes, o2, 0, bucket_offsets, ST(s));
-      });
-      rc != kNoVariant)
+  if (int rc = rows_check(fill)) return rc;
+  if (int rc = bucket_records_impl(keys, keysize, n, nranks, msg_type, src_rank, ht_index, workspace,
+                                   workspace_bytes, records, stride, bucket_offsets, ST(s)))
     return rc;
-  return bucket_impl(keys, keysize, n, nranks, workspace, workspace_bytes, out, 0, bucket_offsets, ST(s));
+  return rows_launch(fill, ST(s), g_kernel);
 }

@@ -108,6 +108,8 @@ extern "C" {
  *                164  two-pass arrays of 8/16-B keys on the balanced digit split
  *                     F = 2^ceil(nbits/2) (product: one fine bit more)
  *   records      112  r02 store order (header halves a staging round early)
+ *   row movers   330  gather / scatter / put values storing with plain instead of
+ *                     non-temporal stores
  *   host          61  chunked copy pipeline instead of zero-copy on pinned buffers
  *   small keys   219  8-B placement with a histogram, 4 keys per lane (the shape
  *                     before late r04; product: 8); 220 16 keys per lane

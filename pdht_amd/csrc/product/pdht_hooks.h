@@ -26,5 +26,7 @@ static inline bool hook_bucket_reserve(bool dflt, size_t) { return dflt; }
 // the fine digit one bit wider for 8/16-B array outputs
 static inline unsigned hook_tl_tile_shift(unsigned dflt, size_t) { return dflt; }
 static inline bool hook_fine_plus(bool dflt) { return dflt; }
+// pdht_rows.hip: non-temporal stores in the row movers
+static inline bool hook_rows_nt(bool dflt) { return dflt; }
 
 }  // namespace pdht

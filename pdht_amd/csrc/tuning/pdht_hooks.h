@@ -35,5 +35,7 @@ static inline unsigned hook_tl_tile_shift(unsigned dflt, size_t keysize) {
 static inline bool hook_fine_plus(bool dflt) {
   return tuning_variant() == 164 || tuning_variant() == 295 ? false : dflt;
 }
+// 330: the row movers' stores in the other policy (plain instead of non-temporal)
+static inline bool hook_rows_nt(bool dflt) { return tuning_variant() == 330 ? !dflt : dflt; }
 
 }  // namespace pdht

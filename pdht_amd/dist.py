@@ -151,7 +151,16 @@ def exchange_records(records, offsets):
     to their owner ranks: ONE all-to-all(v) of the record bytes instead of one
     per payload (exchange_buckets).  Returns (records [m, stride] uint8,
     recv_counts [world]): every record this rank owns, grouped by source rank
-    in rank order, each group in its source's key order."""
+    in rank order, each group in its source's key order.
+
+    The stride is records.shape[1], so put records travel the same way:
+      put: rec, offs = pdht_amd.bucket_put_records(keys, values, world, src_rank=rank)
+           mine, counts = exchange_records(rec, offs)
+           ty, src, ht, idx, mbits, keys, values = pdht_amd.put_record_fields(mine, L, E)
+      get: the owner answers every record where it stands; the replies go back
+           with the splits swapped, arrive in the sender's bucket order (reply p
+           answers its record p) and return to the caller's key order with
+           pdht_amd.scatter_rows(replies, pdht_amd.record_fields(rec, L)[3])."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size()
