@@ -214,5 +214,7 @@ int pdht_hip_key_stream_var_dev(const void *bytes, size_t nbytes, const uint64_t
 /* Put records with values and row gather / scatter in bucket order: same ABI,
  * same libraries, declared (with the record layout) in a header of their own. */
 #include "pdht_hip_put.h"
+/* The device-resident target table: batch put, get and resolve. */
+#include "pdht_hip_table.h"
 
 #endif /* PDHT_HIP_H_ */

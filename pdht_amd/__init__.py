@@ -35,7 +35,7 @@ __all__ = [
     "citycrc128_batch_host", "place_batch_host", "splitmix64_fill", "mixed_lengths",
     "device_count", "PdhtTable", "K2", "bucket_batch", "bucket_records", "record_fields",
     "bucket_record_bytes", "bucket_workspace_bytes", "WeakHashLen32WithSeeds", "WeakHashLen32WithSeeds6",
-    "tuning", "last_kernel", "mpi_lib",
+    "tuning", "last_kernel", "mpi_lib", "table_bytes", "table_reply_bytes", "DeviceTable", "get_resolve",
 ]
 
 K2 = 0x9AE16A3B2F90404F  # city.c:96 (CityHash64WithSeed's seed0)
@@ -121,6 +121,14 @@ def _declare(L, tuning=False):
                                                   _V, _V]),
         "pdht_gather_rows_dev": (C.c_int, [_V, _S, _S, _V, _S, _S, _V, _S, _V]),
         "pdht_scatter_rows_dev": (C.c_int, [_V, _S, _S, _V, _S, _S, _V, _S, _V]),
+        "pdht_table_bytes": (C.c_size_t, [_U64, _S]),
+        "pdht_table_init_dev": (C.c_int, [_V, _S, _U64, _S, _V]),
+        "pdht_table_put_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_put_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _V, _V]),
+        "pdht_table_reply_bytes": (C.c_size_t, [_S, _S]),
+        "pdht_table_get_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _V]),
+        "pdht_table_counts_dev": (C.c_int, [_V, _V, _V]),
+        "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
         "CityHash64WithSeeds": (_U64, [_V, _S, _U64, _U64]),
@@ -711,9 +719,12 @@ def record_fields(records, keysize: int):
 # ------------------------------------------- put records and row movers ---
 # The payload half of bucketing (include/pdht_hip_put.h).
 #   put: bucket_put_records(keys, values, nranks) -> dist.exchange_records
-#        (the stride is records.shape[1]) -> put_record_fields on the receiver;
-#   get: the replies come back in bucket order (reply p answers record p);
-#        scatter_rows(replies, index) puts reply p at row index[p], the
+#        (the stride is records.shape[1]) -> DeviceTable.put_records on the
+#        receiver (or put_record_fields to split them);
+#   get: bucket_records -> dist.exchange_records -> DeviceTable.get ->
+#        dist.exchange_replies: the replies come back in bucket order (reply p
+#        answers record p) -> get_resolve(replies, keys, E, index=...).
+#        scatter_rows(rows, index) puts any row p at row index[p], the
 #        caller's order, index being record_fields(records, L)[3] or
 #        bucket_batch's index output.  gather_rows(rows, index) is the
 #        inverse: rows into bucket order.
@@ -760,8 +771,9 @@ def bucket_put_records(keys, values, nranks: int, *, key_slot: int = 0, msg_type
     value to reuse; `workspace` as for bucket_records
     (bucket_workspace_bytes(n, L, nranks, records=True) bytes).
 
-    Put flow: bucket_put_records -> dist.exchange_records -> put_record_fields.
-    Get flow: the replies return in bucket order -> scatter_rows(replies, index).
+    Put flow: bucket_put_records -> dist.exchange_records -> DeviceTable.put_records.
+    Get flow: bucket_records -> dist.exchange_records -> DeviceTable.get ->
+    dist.exchange_replies (bucket order) -> get_resolve(replies, keys, E, index=...).
     """
     torch = _torch()
     n, L, stride = _keys_2d(keys)
@@ -856,6 +868,205 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
     (None: [m, B], index a permutation).  Rows of out that no index names keep
     their bytes.  check as for gather_rows, against out's rows."""
     return _move_rows(src, index, out, stream, check, True)
+
+
+# ------------------------------------------------- device-resident table ---
+# The owner's side of a put and a get (include/pdht_hip_table.h; the server
+# loop of libmpipdht/init.c:173-290) and the client's resolve (putget.c:50-59).
+#   put: bucket_put_records -> dist.exchange_records -> DeviceTable.put_records
+#   get: bucket_records(msg_type=get) -> dist.exchange_records -> DeviceTable.get
+#        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
+def table_bytes(capacity: int, rowbytes: int) -> int:
+    """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
+    capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
+    b = lib().pdht_table_bytes(capacity, rowbytes)
+    if b == 0:
+        raise ValueError(f"capacity {capacity} must be a power of two in 64 .. 2^31 and rowbytes {rowbytes} "
+                         "a multiple of 8 that is >= 8 and < 2^31")
+    return b
+
+
+def table_reply_bytes(head: int, rowbytes: int) -> int:
+    """Bytes of a get reply: head + rowbytes (head 1 = the packed reply_t of
+    libmpipdht/pdht.h:131-135, head 8 = the aligned form)."""
+    b = lib().pdht_table_reply_bytes(head, rowbytes)
+    if b == 0:
+        raise ValueError(f"head {head} must be 1 or 8 and rowbytes {rowbytes} a multiple of 8 that is >= 8")
+    return b
+
+
+class DeviceTable:
+    """A target table in device memory: opaque rows of `rowbytes` bytes under
+    64-bit mbits (include/pdht_hip_table.h).  For put records rowbytes is the
+    record stride - 24 (key slot + padded value).  `storage`: a uint8 CUDA
+    tensor of at least table_bytes(capacity, rowbytes) bytes, 16-byte aligned
+    (allocated if None); it is emptied here.  Calls on one stream are ordered
+    by the stream; concurrent calls on one table from different streams are
+    undefined."""
+
+    def __init__(self, capacity: int, rowbytes: int, device="cuda", storage=None):
+        torch = _torch()
+        self.capacity, self.rowbytes = int(capacity), int(rowbytes)
+        self.nbytes = table_bytes(self.capacity, self.rowbytes)
+        if storage is None:
+            device = torch.device(device)
+            if device.type != "cuda":
+                raise ValueError("a DeviceTable lives on a CUDA device")
+            if device.index is None:
+                device = torch.device("cuda", torch.cuda.current_device())
+            storage = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        else:
+            if not isinstance(storage, torch.Tensor) or not storage.is_cuda:
+                raise ValueError("storage must be a CUDA uint8 tensor")
+            _need(storage, "storage", torch.uint8, storage.device, numel=self.nbytes)
+            if storage.data_ptr() % 16:
+                raise ValueError("storage must be 16-byte aligned")
+        self.storage = storage
+        self.device = storage.device
+        self.clear()
+
+    def clear(self, stream=None):
+        """Empties the table and its counters (pdht_table_init_dev)."""
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_init_dev(_dptr(self.storage), self.storage.numel(), self.capacity,
+                                             self.rowbytes, g.stream), "pdht_table_init_dev")
+
+    def put_records(self, records, status=True, workspace=None, stream=None):
+        """Applies a batch of put records [m, stride] (uint8, 8-byte aligned,
+        stride >= 24 + rowbytes; bucket_put_records' or forged ones: only the
+        mbits at +16 and the row at +24 are read) as init.c:223-241 would one
+        after the other: the last record of an mbits leaves its row.
+        status: True = return a new uint8 [m] (0 stored / 1 superseded by a
+        later record of the batch / 2 dropped, table full), a uint8 [m] tensor
+        = fill and return it, False / None = none.  workspace: uint8, >= 4*m
+        bytes (allocated if None)."""
+        torch = _torch()
+        m, B, stride = _rows_2d(records, "records", self.device)
+        if B < 24 + self.rowbytes:
+            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
+        if stride % 8 or records.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        if status is True:
+            status = torch.empty(m, dtype=torch.uint8, device=self.device)
+        elif status is False or status is None:
+            status = None
+        else:
+            _need(status, "status", torch.uint8, self.device, shape=(m,))
+        need = lib().pdht_table_put_workspace_bytes(m)
+        if workspace is None:
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 4:
+                raise ValueError("workspace must be 4-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_put_records_dev(_dptr(self.storage), self.capacity, self.rowbytes,
+                                                    _dptr(records), stride, m, _dptr(workspace),
+                                                    workspace.numel(), _opt(status), g.stream),
+                   "pdht_table_put_records_dev")
+        return status
+
+    def get(self, mbits_or_records, head: int = 8, out=None, stream=None):
+        """Answers a batch of requests as init.c:192-220 does: replies uint8
+        [m, head + rowbytes], byte 0 = 1 found / 0 not found, bytes 1..head-1
+        zero, then the row (zeros when not found).  A 1-D int64 tensor is read
+        as dense mbits; a 2-D uint8 record batch (bucket_records' or put
+        records) is read in place at +16 with its row stride.  out: a uint8
+        [m, head + rowbytes] tensor or row-strided view at any address; bytes
+        outside its rows are not written."""
+        torch = _torch()
+        t = mbits_or_records
+        rb = table_reply_bytes(head, self.rowbytes)
+        if isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int64:
+            _need(t, "mbits", torch.int64, self.device)
+            m, ptr, stride = t.numel(), t.data_ptr(), 8
+        elif isinstance(t, torch.Tensor) and t.dim() == 2 and t.dtype == torch.uint8:
+            m, B, stride = _rows_2d(t, "records", self.device)
+            if B < 24:
+                raise ValueError(f"records must have >= 24 bytes per row, got {B}")
+            if stride % 8 or t.data_ptr() % 8:
+                raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+            ptr = t.data_ptr() + 16
+        else:
+            raise ValueError("expected a 1-D int64 tensor of mbits or a 2-D uint8 record batch")
+        if out is None:
+            out = torch.empty((m, rb // 8 if head == 8 else rb), dtype=torch.int64 if head == 8 else torch.uint8,
+                              device=self.device).view(torch.uint8).view(m, rb)
+        om, oB, ostride = _rows_2d(out, "out", self.device)
+        if (om, oB) != (m, rb):
+            raise ValueError(f"out must have shape [{m}, {rb}], got {tuple(out.shape)}")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_get_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
+                                            stride, m, _dptr(out), ostride, head, g.stream), "pdht_table_get_dev")
+        return out
+
+    def counts_dev(self, out=None, stream=None):
+        """The four counters as an int64 [4] CUDA tensor, asynchronously."""
+        torch = _torch()
+        if out is None:
+            out = torch.empty(4, dtype=torch.int64, device=self.device)
+        _need(out, "out", torch.int64, self.device, shape=(4,))
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_counts_dev(_dptr(self.storage), _dptr(out), g.stream), "pdht_table_counts_dev")
+        return out
+
+    def counts(self):
+        """(entries stored, records dropped, put batches applied, slots
+        inspected by puts); the last three cumulative.  Host-synchronous."""
+        return tuple(int(x) for x in self.counts_dev().cpu().tolist())
+
+
+def get_resolve(replies, keys, elemsize: int, *, head: int = 8, key_slot: int = 0, index=None, values=None,
+                status=None, stream=None):
+    """The client's side of a get batch (pdht_get_resolve_dev; putget.c:50-59):
+    replies uint8 [m, >= head + slot + elemsize] in bucket order, as
+    DeviceTable.get wrote them and dist.exchange_replies brought them back;
+    keys uint8 [n, L] packed, the caller's keys; slot = key_slot or L rounded
+    up to 8.  With i = index[p] (int32 [m], e.g. record_fields(records, L)[3]
+    read in place; None: i = p), status[i] = 2 NotFound / 3 Collision (the
+    reply's key differs from keys[i]) / 0 OK, and values[i] receives the
+    reply's value when 0.  Returns (values uint8 [n, elemsize], status uint8
+    [n]); rows that no OK reply names keep their bytes (new tensors start as
+    zeros, and status as 2).  values may be a row-strided view."""
+    torch = _torch()
+    m, RB, rstride = _rows_2d(replies, "replies")
+    dev = replies.device
+    n, L, kstride = _keys_2d(keys)
+    if keys.device != dev or kstride != L:
+        raise ValueError(f"keys must be packed and on {dev}")
+    if head not in (1, 8):
+        raise ValueError("head must be 1 or 8")
+    if elemsize < 1:
+        raise ValueError("elemsize must be >= 1")
+    if key_slot and (key_slot % 8 or key_slot < L):
+        raise ValueError(f"key_slot {key_slot} must be 0 or a multiple of 8 that is >= keysize {L}")
+    slot = key_slot if key_slot else (L + 7) // 8 * 8
+    if RB < head + slot + elemsize:
+        raise ValueError(f"replies must have >= {head + slot + elemsize} bytes per row, got {RB}")
+    if index is not None:
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or index.dim() != 1 or \
+                not index.is_cuda or index.device != dev or index.numel() != m:
+            raise ValueError(f"index must be a 1-D int32 tensor of {m} entries on {dev}")
+        istride = 4 * index.stride(0) if m > 1 else 4
+        if istride < 4:
+            raise ValueError("index must have a positive stride")
+    else:
+        istride = 4
+        if m > n:
+            raise ValueError(f"{m} replies for {n} keys")
+    if values is None:
+        values = torch.zeros((n, elemsize), dtype=torch.uint8, device=dev)
+    vn, vE, vstride = _rows_2d(values, "values", dev)
+    if (vn, vE) != (n, elemsize):
+        raise ValueError(f"values must have shape [{n}, {elemsize}], got {tuple(values.shape)}")
+    if status is None:
+        status = torch.full((n,), 2, dtype=torch.uint8, device=dev)
+    _need(status, "status", torch.uint8, dev, shape=(n,))
+    with _on(dev, stream) as g:
+        _check(lib().pdht_get_resolve_dev(_dptr(replies), rstride, head, slot, _dptr(keys), L, _opt(index), istride,
+                                          m, _dptr(values), elemsize, vstride, _dptr(status), g.stream),
+               "pdht_get_resolve_dev")
+    return values, status
 
 
 def splitmix64_fill(seed: int, first: int, nwords: int, out=None, device="cuda", stream=None):

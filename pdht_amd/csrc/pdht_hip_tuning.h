@@ -110,6 +110,8 @@ extern "C" {
  *   records      112  r02 store order (header halves a staging round early)
  *   row movers   330  gather / scatter / put values storing with plain instead of
  *                     non-temporal stores
+ *   table        340  get replies stored plain (product: non-temporal)
+ *                341  put rows stored plain (product: non-temporal)
  *   host          61  chunked copy pipeline instead of zero-copy on pinned buffers
  *   small keys   219  8-B placement with a histogram, 4 keys per lane (the shape
  *                     before late r04; product: 8); 220 16 keys per lane

@@ -28,5 +28,8 @@ static inline unsigned hook_tl_tile_shift(unsigned dflt, size_t) { return dflt; 
 static inline bool hook_fine_plus(bool dflt) { return dflt; }
 // pdht_rows.hip: non-temporal stores in the row movers
 static inline bool hook_rows_nt(bool dflt) { return dflt; }
+// pdht_table.hip: non-temporal stores of the get replies / of a put's rows
+static inline bool hook_table_reply_nt(bool dflt) { return dflt; }
+static inline bool hook_table_put_nt(bool dflt) { return dflt; }
 
 }  // namespace pdht

@@ -37,5 +37,8 @@ static inline bool hook_fine_plus(bool dflt) {
 }
 // 330: the row movers' stores in the other policy (plain instead of non-temporal)
 static inline bool hook_rows_nt(bool dflt) { return tuning_variant() == 330 ? !dflt : dflt; }
+// 340 / 341: the table's get replies / put rows stored in the other policy
+static inline bool hook_table_reply_nt(bool dflt) { return tuning_variant() == 340 ? !dflt : dflt; }
+static inline bool hook_table_put_nt(bool dflt) { return tuning_variant() == 341 ? !dflt : dflt; }
 
 }  // namespace pdht

@@ -157,10 +157,13 @@ def exchange_records(records, offsets):
       put: rec, offs = pdht_amd.bucket_put_records(keys, values, world, src_rank=rank)
            mine, counts = exchange_records(rec, offs)
            ty, src, ht, idx, mbits, keys, values = pdht_amd.put_record_fields(mine, L, E)
-      get: the owner answers every record where it stands; the replies go back
-           with the splits swapped, arrive in the sender's bucket order (reply p
-           answers its record p) and return to the caller's key order with
-           pdht_amd.scatter_rows(replies, pdht_amd.record_fields(rec, L)[3])."""
+           table.put_records(mine)                       # pdht_amd.DeviceTable, the owner's side
+      get: rec, offs = pdht_amd.bucket_records(keys, world, msg_type=get, src_rank=rank)
+           asked, counts = exchange_records(rec, offs)
+           replies = table.get(asked)                    # one reply per record, where it stands
+           back = exchange_replies(replies, offs, counts)  # the splits swapped
+           values, status = pdht_amd.get_resolve(back, keys, E, index=pdht_amd.record_fields(rec, L)[3])
+           (reply p answers the sender's record p; get_resolve puts it at the caller's row)."""
     import torch
     import torch.distributed as dist
     world = dist.get_world_size()
@@ -175,6 +178,31 @@ def exchange_records(records, offsets):
     out = torch.empty(sum(r_split), dtype=torch.uint8, device=records.device)
     dist.all_to_all_single(out, records.contiguous().view(-1), r_split, s_split)
     return out.view(-1, rb), recv
+
+
+def exchange_replies(replies, offsets, recv_counts):
+    """Send get replies back to the ranks that asked: the all-to-all(v) of
+    exchange_records with the splits swapped.  replies [m, reply bytes]: one
+    row per record exchange_records delivered here, in that order
+    (pdht_amd.DeviceTable.get answers them where they stand); offsets: this
+    rank's own bucket offsets, as passed to exchange_records; recv_counts: what
+    exchange_records returned.  Returns replies [n, reply bytes] in this rank's
+    bucket order: reply p answers its record p, and pdht_amd.get_resolve (or
+    scatter_rows) takes it to the caller's key order."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size()
+    if offsets.numel() != world + 1 or recv_counts.numel() != world:
+        raise ValueError("offsets and recv_counts must come from exchange_records on this world")
+    rb = replies.shape[1]
+    back = (offsets[1:] - offsets[:-1]).to(torch.int64)
+    s_split = [int(x) * rb for x in recv_counts.cpu().tolist()]
+    r_split = [int(x) * rb for x in back.cpu().tolist()]
+    if replies.shape[0] * rb != sum(s_split):
+        raise ValueError(f"{replies.shape[0]} replies for {sum(s_split) // max(rb, 1)} records received")
+    out = torch.empty(sum(r_split), dtype=torch.uint8, device=replies.device)
+    dist.all_to_all_single(out, replies.contiguous().view(-1), r_split, s_split)
+    return out.view(-1, rb)
 
 
 def device_info(device=None) -> dict:
