@@ -124,7 +124,14 @@ int pdht_place_batch_dev(const void *keys, size_t keysize, size_t n,
  * (device) must hold pdht_bucket_workspace_bytes(n, keysize, nranks): the
  * per-tile counts and, for 8/16/32-B keys at the rank counts that take the
  * two-pass sort (from 1575 / 1575 / 2049 ranks for 8 / 16 / 32-B keys), its
- * intermediate (about n x (keysize + 2) bytes). */
+ * intermediate (about n x (keysize + 2) bytes).  Alignment, checked before
+ * any launch (a misaligned pointer is refused, pdht_hip_last_error() names
+ * the argument): workspace 16 bytes (its counters and totals are uint32 /
+ * uint64, and the two-pass key rows are read as 16-byte vectors); mbits_out
+ * and bucket_offsets 8 bytes; ptindex_out and index_out 4 bytes.  keys and
+ * keys_out may start at any address: 8-B keys off an 8-byte boundary, or
+ * 16/32-B keys off a 16-byte one, in either, take the generic-length kernel.
+ * The workspace's contents on entry do not matter and are not preserved. */
 size_t pdht_bucket_workspace_bytes(size_t n, size_t keysize, uint32_t nranks);
 int pdht_bucket_batch_dev(const void *keys, size_t keysize, size_t n,
                           uint32_t nptes, uint32_t nranks, void *workspace,
@@ -148,8 +155,9 @@ int pdht_bucket_batch_dev(const void *keys, size_t keysize, size_t n,
  *   +24 key[keysize], zero-padded to the stride.
  * records (device, 8-byte aligned) holds n records; bucket_offsets as for
  * pdht_bucket_batch_dev, the workspace sized by
- * pdht_bucket_records_workspace_bytes.  ptindex is not stored (it is
- * mbits % nptes; the MPI message carries ht_index instead). */
+ * pdht_bucket_records_workspace_bytes and, like bucket_offsets, aligned as
+ * for pdht_bucket_batch_dev (16 and 8 bytes; refused otherwise).  ptindex is
+ * not stored (it is mbits % nptes; the MPI message carries ht_index instead). */
 size_t pdht_bucket_record_bytes(size_t keysize);
 /* Workspace of pdht_bucket_records_dev: as pdht_bucket_workspace_bytes, with
  * the records' two-pass thresholds (from 2048 / 1463 / 256 ranks for 8 / 16 /

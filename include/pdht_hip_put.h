@@ -61,8 +61,9 @@ int pdht_scatter_rows_dev(const void *src, size_t src_stride, size_t rowbytes,
  * be 0 or a multiple of 8 that is >= keysize (the size query returns 0
  * otherwise).  Every byte of every record is defined on return.  records
  * (device, 8-byte aligned) holds n records; the workspace is sized by
- * pdht_bucket_records_workspace_bytes, bucket_offsets as for
- * pdht_bucket_batch_dev.  Two kernels run on the stream, the bucketing kernel
+ * pdht_bucket_records_workspace_bytes and must be 16-byte aligned,
+ * bucket_offsets (8-byte aligned) as for pdht_bucket_batch_dev; a misaligned
+ * one is refused before any launch.  Two kernels run on the stream, the bucketing kernel
  * and the value mover; pdht_hip_last_kernel() names both, e.g.
  * "k_bucket_scatter_staged<8B>+k_rows_gather<8>". */
 size_t pdht_bucket_put_record_bytes(size_t keysize, size_t key_slot, size_t elemsize);

@@ -617,6 +617,8 @@ def _workspace(workspace, n, L, nranks, dev, records=False):
     if workspace is None:
         return torch.empty(max(need, 1), dtype=torch.uint8, device=dev), need
     _need(workspace, "workspace", torch.uint8, dev, numel=need)
+    if workspace.data_ptr() % 16:
+        raise ValueError("workspace must be 16-byte aligned")
     return workspace, workspace.numel()
 
 

@@ -282,7 +282,9 @@ __global__ __launch_bounds__(kBaseThreads) void k_bucket_base(const u64 *__restr
   __shared__ u64 scratch[kBaseThreads / 64];
   static_assert(sizeof(tot) + sizeof(scratch) <= 160 * 1024, "gfx950 LDS per workgroup");
   if (tickets && threadIdx.x < 16) tickets[threadIdx.x] = 0;  // per-XCD tile tickets of the scatter kernels
-  for (u32 r = threadIdx.x; r < nranks; r += kBaseThreads) tot[r] = totals[r];
+  // totals == nullptr: an empty batch, every total 0 (no memset ahead of this kernel: as a node of a captured
+  // graph it left the totals as they were on replay, tests/test_gpu_bucket_buffers.py)
+  for (u32 r = threadIdx.x; r < nranks; r += kBaseThreads) tot[r] = totals ? totals[r] : 0;
   __syncthreads();
   constexpr u32 kMaxPer = kBucketMaxRanks / kBaseThreads;
   const u32 per = (nranks + kBaseThreads - 1) / kBaseThreads;

@@ -365,6 +365,10 @@ static int bucket_impl(const void *keys, size_t keysize, size_t n, uint32_t nran
   if (nranks > kBucketMaxRanks) return fail("bucketing supports up to 8192 ranks%s", "");
   if (n >= (1ull << 32)) return fail("bucketing: n must be < 2^32 per call%s", "");
   if (!bucket_offsets) return fail("bucket_offsets must not be NULL%s", "");
+  if ((uintptr_t)bucket_offsets & 7) return fail("bucket_offsets must be 8-byte aligned%s", "");
+  // the workspace's pieces start at multiples of 256 B from its base: u32 counters, u64 totals, the tickets'
+  // atomics, and the two-pass key rows, which load_key_regs reads as 16-B vectors (the widest access to it)
+  if ((uintptr_t)workspace & 15) return fail("workspace must be 16-byte aligned%s", "");
   if (n && (!keys || keysize == 0)) return fail("null keys or zero keysize%s", "");
   const BucketWs w = bucket_layout(workspace, n, keysize, nranks, Out::kPair8);
   if (!workspace || workspace_bytes < w.bytes) return fail("workspace too small%s", "");
@@ -390,9 +394,8 @@ static int bucket_impl(const void *keys, size_t keysize, size_t n, uint32_t nran
   if (kind == BucketKernel::kTwoPass) {
     if (int rc = hook_two_pass_r05(a, w, keysize, out, bucket_offsets, st, dev); rc != kNoVariant) {
       if (rc) return rc;
-    } else if (n == 0) {
-      HIP_TRY(hipMemsetAsync(w.totals, 0, (size_t)nranks * 8, st));
-      k_bucket_base<<<1, kBaseThreads, 0, st>>>(w.totals, nranks, w.base, bucket_offsets, nullptr);
+    } else if (n == 0) {  // (no totals: k_bucket_base reads them as zeros)
+      k_bucket_base<<<1, kBaseThreads, 0, st>>>(nullptr, nranks, w.base, bucket_offsets, nullptr);
       g_kernel = "k_bucket_base";
     } else if (int rc = bucket_tl(a, w, keysize, out, bucket_offsets, st, dev)) {
       return rc;
@@ -419,10 +422,8 @@ static int bucket_impl(const void *keys, size_t keysize, size_t n, uint32_t nran
       k_bucket_count<<<gc, kBlock, hist_lds, st>>>(a.k, (u32)keysize, n, a.rk, nranks, w.counts, ntiles, tile);
     k_bucket_colscan<<<dim3((nranks + 63) / 64, (unsigned)nchunks), 64, 0, st>>>(w.counts, ntiles, nranks, w.chunks);
     k_bucket_chunkscan<<<(nranks + 63) / 64, 64 * kCsWaves, 0, st>>>(w.chunks, nchunks, nranks, w.totals);
-  } else {
-    HIP_TRY(hipMemsetAsync(w.totals, 0, (size_t)nranks * 8, st));
   }
-  k_bucket_base<<<1, kBaseThreads, 0, st>>>(w.totals, nranks, w.base, bucket_offsets, w.tickets);
+  k_bucket_base<<<1, kBaseThreads, 0, st>>>(ntiles ? w.totals : nullptr, nranks, w.base, bucket_offsets, w.tickets);
   g_kernel = "k_bucket_base";
   if (ntiles) {
     int rc = hook_staged_launch(kind == BucketKernel::kStaged, keysize, a, out, st, dev, shape, w.tickets);
@@ -458,6 +459,9 @@ PDHT_API int pdht_bucket_batch_dev(const void *keys, size_t keysize, size_t n, u
                                    uint32_t *index_out, uint64_t *bucket_offsets,
                                    pdht_hip_stream_t s) {
   if (int rc = check_place(n, mbits_out, nptes, nranks, nullptr, 0)) return rc;
+  if ((uintptr_t)mbits_out & 7) return fail("mbits_out must be 8-byte aligned%s", "");
+  if ((uintptr_t)ptindex_out & 3) return fail("ptindex_out must be 4-byte aligned%s", "");
+  if ((uintptr_t)index_out & 3) return fail("index_out must be 4-byte aligned%s", "");
   const OutSoA out{static_cast<uint8_t *>(keys_out), mbits_out, ptindex_out, index_out, make_fastmod(nptes),
                    (u32)keysize};
   return bucket_impl(keys, keysize, n, nranks, workspace, workspace_bytes, out, (uintptr_t)keys_out,

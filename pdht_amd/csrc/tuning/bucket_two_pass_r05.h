@@ -517,10 +517,8 @@ static int bucket_r05(const BucketArgs &a0, const BucketWs &w, size_t keysize, c
     const u32 nbF = (tp.F + 63) / 64;  // both chunk scans in one launch
     k_bucket_chunkscan2<<<nbF + (nranks + 63) / 64, 64 * kCsWaves, 0, st>>>(
         r.chunksF, nfchunks, tp.F, r.totalsF, nbF, r.chunkcnt, tp.nchunks, nranks, w.totals);
-  } else {
-    HIP_TRY(hipMemsetAsync(w.totals, 0, (size_t)nranks * 8, st));
   }
-  k_bucket_base<<<1, kBaseThreads, 0, st>>>(w.totals, nranks, w.base, bucket_offsets, nullptr);
+  k_bucket_base<<<1, kBaseThreads, 0, st>>>(ntiles ? w.totals : nullptr, nranks, w.base, bucket_offsets, nullptr);
   g_kernel = "k_bucket_base";
   if (!ntiles) return 0;
   k_bucket_fbase<<<1, kTpMaxDigits, 0, st>>>(r.totalsF, tp.F, r.fbase);

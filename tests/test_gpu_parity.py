@@ -9,6 +9,7 @@ All calls go through the C-ABI (pdht_amd -> libpdht_hip.so).
 import numpy as np
 import pytest
 
+from bucket_ref import _bucket_kernel
 from conftest import pattern_a
 
 torch = pytest.importorskip("torch")
@@ -606,44 +607,6 @@ BUCKET_CASES += [(L, nr, n, 0) for L in (8, 32) for nr in (2049, 8192) for n in 
 # 291-293: tile-local shapes (pass 2 in 4 x 8 @ 4 / 8 x 4 @ 2; pass 1 in 16 waves @ 1)
 BUCKET_CASES += [(L, nr, n, v) for v in (290, 291, 292, 293, 302, 304, 305, 316, 318, 320, 322, 323) for L in (8, 16, 32) for nr in (2049, 8192)
                  for n in (4095, 300007, (1 << 20) + 5)]
-
-
-def _bucket_kernel(L, nranks, variant, records=False):
-    """Product: the staged scatter for 8/16/32-B keys below the two-pass
-    threshold (arrays 1575 / 1575 / 2049 ranks, records 2048 / 1463 / 256 for
-    8 / 16 / 32-B keys), two passes from it, the generic
-    kernel for other lengths.  Tuning variants: 21 forces the generic-length
-    kernel, 70 one pass up to 2048 ranks, 71 two passes from 2 ranks up, 85
-    the staged scatter in the static tile order instead of per-XCD tickets,
-    83 / 87 / 89 the staged scatter with owner-table ranking on 8 x 16 / 4 x
-    16 tiles or with ballots, at any nranks."""
-    wg = "k_bucket_scatter_wg<8>" if nranks <= 4096 else "k_bucket_scatter_wg<4>"
-    if variant == 21:
-        return wg
-    if L in (8, 16, 32):
-        two_pass_from = ({8: 2048, 16: 1463, 32: 256} if records else {8: 1575, 16: 1575, 32: 2049})[L]
-        one_pass = variant == 70 and nranks <= 2048
-        if (variant == 71 and nranks >= 2) or (not one_pass and nranks >= two_pass_from):
-            # the tile-local form (r06); the r02-r05 form under 290 and its shape variants
-            r05 = variant in (290, 202, 264) or 265 <= variant <= 272
-            return f"k_bucket_pass2<{L}B>" if r05 else f"k_bucket_tl_pass2<{L}B>"
-        # staged_shape(): owner-table ranking for array outputs from 512
-        # ranks, on 8 x 16 tiles for 8/16-B keys while 81920 + 52 B per rank
-        # of dynamic LDS and the kernel's 40 fixed bytes fit a CU, else on
-        # 4 x 16 tiles while 40960 + 28 B per rank stay within 80 KiB;
-        # ballots otherwise
-        if variant == 83:
-            return f"k_bucket_scatter_staged<{L}B,own,8x16>"
-        if variant == 87:
-            return f"k_bucket_scatter_staged<{L}B,own>"
-        if variant in (85, 89) or records or nranks < 512:
-            return f"k_bucket_scatter_staged<{L}B>"
-        if L != 32 and 81920 + 52 * nranks + 40 <= 160 * 1024:
-            return f"k_bucket_scatter_staged<{L}B,own,8x16>"
-        if 40960 + 28 * nranks <= 80 * 1024:
-            return f"k_bucket_scatter_staged<{L}B,own>"
-        return f"k_bucket_scatter_staged<{L}B>"
-    return wg
 
 
 def _tuning_marked(cases):

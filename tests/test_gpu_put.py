@@ -178,12 +178,11 @@ def test_scatter_rows_padded_dst(dev, B, m, pad, off):
 
 # ------------------------------------------------------------- put records ---
 def _bucket_kernel(L, nranks):
-    """The product's bucketing kernel for records (test_gpu_parity.py _bucket_kernel(..., records=True),
+    """The product's bucketing kernel for records (bucket_ref.py _bucket_kernel(..., records=True),
     variant 0): the staged scatter for 8/16/32-B keys below 2048 / 1463 / 256 ranks, two passes from there,
     the generic kernel for other lengths.  The staged shape is staged_shape()'s (pdht_bucket.hip): records
     rank by ballots below 512 ranks and by owner tables on 4 x 16 tiles from there while 40960 + 28 B per
-    rank of dynamic LDS stay within 80 KiB -- that helper's records branch names ballots at any rank count,
-    which no test there asserts and the library does not do (RECORD_CASES' own comment says so)."""
+    rank of dynamic LDS stay within 80 KiB."""
     wg = "k_bucket_scatter_wg<8>" if nranks <= 4096 else "k_bucket_scatter_wg<4>"
     if L in (8, 16, 32):
         if nranks >= {8: 2048, 16: 1463, 32: 256}[L]:
