@@ -61,6 +61,7 @@ $(LIBDIR)/pdht_bucket.o $(LIBDIR)/pdht_bucket.tun.o: pdht_amd/csrc/bucket.h pdht
 $(LIBDIR)/pdht_rows.o $(LIBDIR)/pdht_rows.tun.o: pdht_amd/csrc/rows.h
 $(LIBDIR)/pdht_table.o $(LIBDIR)/pdht_table.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/rows.h
 $(foreach u,pdht_fixed64 pdht_fixed128 pdht_var pdht_host,$(LIBDIR)/$(u).o $(LIBDIR)/$(u).tun.o): pdht_amd/csrc/launch.h
+$(LIBDIR)/pdht_host.o $(LIBDIR)/pdht_host.tun.o: pdht_amd/csrc/host_chunks.h
 
 # (product objects never see the tuning headers, and the reverse)
 $(LIBDIR)/%.o: pdht_amd/csrc/%.hip $(HIP_HDR) $(HDR_PRODUCT)

@@ -1,5 +1,6 @@
 // pdht_host.hip -- host-resident batches (include/pdht_hip.h): zero-copy
 // kernels on pinned buffers, a chunked copy pipeline for pageable ones.
+#include "host_chunks.h"
 #include "launch.h"
 
 namespace pdht {
@@ -310,22 +311,8 @@ PDHT_API int pdht_city64_batch_var_host(const void *bytes, const uint64_t *offse
   const size_t max_keys = kChunkBytes / 16;
   // chunk c covers keys [a, b) with at most kChunkBytes of key bytes (a key
   // longer than that gets a chunk of its own and a larger buffer)
-  size_t next = 0;
   std::vector<std::pair<size_t, size_t>> chunks;
-  while (next < n) {
-    size_t a = next, b = a + 1;
-    const u64 lim = offsets[a] + kChunkBytes;
-    size_t hi = std::min(n, a + max_keys);
-    // largest b <= hi with offsets[b] <= lim (binary search; offsets sorted)
-    size_t lo_b = a + 1, hi_b = hi;
-    while (lo_b < hi_b) {
-      size_t mid = (lo_b + hi_b + 1) / 2;
-      if (offsets[mid] <= lim) lo_b = mid; else hi_b = mid - 1;
-    }
-    b = std::max(a + 1, lo_b);
-    chunks.push_back({a, b});
-    next = b;
-  }
+  host_var_chunks(offsets, n, kChunkBytes, max_keys, chunks);
   auto plan = [&](size_t c, size_t *a, size_t *b) {
     if (c >= chunks.size()) return false;
     *a = chunks[c].first;
