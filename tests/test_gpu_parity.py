@@ -11,6 +11,7 @@ import pytest
 
 from bucket_ref import _bucket_kernel
 from conftest import pattern_a
+from hash_ref import fixed_kernel
 
 torch = pytest.importorskip("torch")
 import pdht_amd as P  # noqa: E402
@@ -58,17 +59,6 @@ def test_generator_matches_oracle(dev, oracle):
 
 SMALL_KERNELS = {8: "k_fixed_direct<8,4,nt>@8", 16: "k_fixed_direct<16,2,nt>@8",
                  32: "k_fixed_direct<32,2,nt>@8", 64: "k_fixed_xpose64<nt,d2>@3"}
-
-
-def fixed_kernel(L, stride=None, aligned=True, crc=False):
-    """launch_fixed's choice for a generic length: the LDS window that holds a
-    64-key tile (12 KiB or 16 KiB), else per-lane global reads (16-B loads
-    when every key starts 16-B aligned; 2 WG/CU, 8 with the LDS CRC tables)."""
-    tile = 63 * (stride or L) + L + 16
-    if tile > 16384:
-        a16 = aligned and (stride or L) % 16 == 0
-        return ("k_global<fixed,a16,lines>" if a16 else "k_global<fixed>") + ("@8" if crc and L > 900 else "@2")
-    return "k_window<fixed,nt,16K>@2" if tile > 12288 else "k_window<fixed,nt,12K>@3"
 
 
 @pytest.mark.parametrize("L", list(range(0, 300)) + [511, 512, 899, 900, 901, 1000, 2047, 4097])
