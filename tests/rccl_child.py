@@ -2,8 +2,9 @@
 an RCCL ("nccl") process group of world size 1 on cuda:0, running the N-rank
 code paths of pdht_amd.dist on device tensors -- the exchange of bucketed
 keys and of wire records (all_to_all_single, the one collective the path
-has: libmpipdht/putget.c:80-100 ships each request to its owner), the
-reductions and the per-rank report.  Started as a fresh process, before
+has: libmpipdht/putget.c:80-100 ships each request to its owner), the whole
+put and get flow through them (exchange_replies included), the reductions
+and the per-rank report.  Started as a fresh process, before
 anything in it touches the GPU; prints one JSON line."""
 import json
 import os
@@ -40,6 +41,31 @@ def main():
     rec, roffs = P.bucket_records(keys, 1)
     xr, rrecv = D.exchange_records(rec, roffs)
     res["exchange_records"] = bool(xr.is_cuda and torch.equal(xr, rec) and rrecv.tolist() == [n])
+
+    # the whole put and get flow through the collectives: the first exchange_replies on device tensors
+    E, extra = 12, 1000
+    values = P.splitmix64_fill(0x0DDBA11, 0, 2 * n, device=dev).view(torch.uint8).view(n, 16)[:, 3:3 + E]
+    prec, poffs = P.bucket_put_records(keys, values, 1, src_rank=0)
+    mine, pcounts = D.exchange_records(prec, poffs)
+    table = P.DeviceTable(1 << 18, mine.shape[1] - 24, dev)
+    status = table.put_records(mine)  # splitmix64 is a bijection: the n keys are distinct
+    never = P.splitmix64_fill(0x5EED5EED5EED5EED, n, extra, device=dev).view(torch.uint8).view(extra, L)
+    order = torch.randperm(n + extra, generator=torch.Generator().manual_seed(7)).to(dev)
+    asked_keys = torch.cat([keys, never])[order].contiguous()
+    ask, aoffs = P.bucket_records(asked_keys, 1, msg_type=0, src_rank=0)  # 0 = pdhtGet
+    asked, acounts = D.exchange_records(ask, aoffs)
+    replies = table.get(asked)
+    back = D.exchange_replies(replies, aoffs, acounts)
+    sentinel = torch.full((n + extra, E), 0xC3, dtype=torch.uint8, device=dev)
+    got, gstatus = P.get_resolve(back, asked_keys, E, index=P.record_fields(ask, L)[3], values=sentinel)
+    was_put = order < n
+    want = torch.full((n + extra, E), 0xC3, dtype=torch.uint8, device=dev)
+    want[was_put] = values[order[was_put]]
+    res["put_get_flow"] = bool(mine.is_cuda and back.is_cuda and pcounts.tolist() == [n]
+                               and acounts.tolist() == [n + extra] and int(status.count_nonzero()) == 0
+                               and table.counts()[:3] == (n, 0, 1) and torch.equal(back, replies)
+                               and torch.equal(gstatus, torch.where(was_put, 0, 2).to(torch.uint8))
+                               and torch.equal(got, want))
 
     # reductions and the per-rank report on device tensors
     res["allreduce_max"] = D.allreduce_max([1.5, 2.25], device=dev) == [1.5, 2.25]

@@ -38,11 +38,14 @@ def _child(cmd, timeout):
 def test_rccl_world1_exchange_and_reductions():
     """exchange_buckets / exchange_records (all_to_all_single), allreduce_max,
     allreduce_fold, allreduce_min_int and per_rank_report through RCCL on
-    device tensors; RCCL is mapped in the child."""
+    device tensors; RCCL is mapped in the child.  put_get_flow: bucket_put_records
+    -> exchange_records -> DeviceTable.put_records, then bucket_records(get) ->
+    exchange_records -> get -> exchange_replies -> get_resolve, every key that
+    was put back OK with its value and every other NotFound."""
     r = _child([sys.executable, "-u", os.path.join(ROOT, "tests", "rccl_child.py"), _port()], 110)
     assert r["backend"] == "nccl" and r["world"] == 1
-    for k in ("exchange_buckets", "exchange_records", "allreduce_max", "allreduce_fold", "allreduce_min_int",
-              "per_rank_report", "rccl_mapped", "product_mapped"):
+    for k in ("exchange_buckets", "exchange_records", "put_get_flow", "allreduce_max", "allreduce_fold",
+              "allreduce_min_int", "per_rank_report", "rccl_mapped", "product_mapped"):
         assert r[k] is True, (k, r)
 
 
