@@ -30,10 +30,11 @@ CFLAGS_SHIM = -std=c99 -O3 -fPIC -fvisibility=hidden -Wall -Wextra -Iinclude
 
 HIP_HDR := pdht_amd/csrc/city_core.h pdht_amd/csrc/kernels.h pdht_amd/csrc/runtime.h \
            pdht_amd/csrc/bucket.h pdht_amd/csrc/launch.h include/pdht_hip.h include/pdht_hip_put.h \
-           include/pdht_hip_table.h include/pdht_city.h
+           include/pdht_hip_table.h include/pdht_hip_plan.h include/pdht_city.h
 HDR_PRODUCT := $(wildcard pdht_amd/csrc/product/*.h)
 HDR_TUNING := $(wildcard pdht_amd/csrc/tuning/*.h) pdht_amd/csrc/pdht_hip_tuning.h
 SHIM_HDR := include/pdht_hash.h include/pdht_hip.h include/pdht_hip_put.h include/pdht_hip_table.h \
+            include/pdht_hip_plan.h \
             include/pdht_city.h
 # the C-ABI in translation units that build in parallel (make -j)
 HIP_UNITS := pdht_hip pdht_fixed64 pdht_fixed128 pdht_var pdht_host pdht_bucket pdht_rows pdht_table

@@ -85,6 +85,12 @@ EXP_LIB_PATH = os.path.join(HERE, "lib", "libpdht_hip_exp.so")
 MPI_LIB_PATH = os.path.join(HERE, "lib", "libpdht_hip_mpi.so")
 
 
+class Xpose64Plan(C.Structure):
+    """pdht_hip_xpose64_plan (pdht_hip.h): the 64-B kernel's launch plan."""
+    _fields_ = [("grid", C.c_uint64), ("rounds", C.c_uint64), ("launches", C.c_uint64), ("waves", C.c_uint32),
+                ("rounds_per_wg", C.c_uint32), ("round_blocked", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _declare(L, tuning=False):
     sig = {
         "pdht_hip_version": (C.c_char_p, []),
@@ -111,6 +117,8 @@ def _declare(L, tuning=False):
         "pdht_hip_read_stream_dev": (C.c_int, [_V, _S, C.c_int, _V, _V]),
         "pdht_hip_key_stream_dev": (C.c_int, [_V, _S, _V, _V]),
         "pdht_hip_key_stream_var_dev": (C.c_int, [_V, _S, _V, _S, _V, _V]),
+        "pdht_hip_xpose64_plan_for": (C.c_int, [_S, C.c_int, C.c_int, C.c_int, C.POINTER(Xpose64Plan)]),
+        "pdht_hip_xpose64_tiles": (C.c_int, [C.POINTER(Xpose64Plan), _U64, _S, _V]),
         "pdht_bucket_workspace_bytes": (C.c_size_t, [_S, _S, _U32]),
         "pdht_bucket_records_workspace_bytes": (C.c_size_t, [_S, _S, _U32]),
         "pdht_bucket_batch_dev": (C.c_int, [_V, _S, _S, _U32, _U32, _V, _S, _V, _V, _V, _V, _V, _V]),
@@ -1107,6 +1115,31 @@ def key_stream(keys, out=None, stream=None):
     with _on(keys.device, stream) as g:
         _check(lib().pdht_hip_key_stream_dev(_dptr(keys), n, _dptr(out), g.stream), "pdht_hip_key_stream_dev")
     return out
+
+
+def xpose64_plan(n: int, cus: int = None, rounds_per_wg: int = -1, hist: bool = False) -> Xpose64Plan:
+    """Launch plan of the default 64-B kernel over n packed keys (pdht_hip.h,
+    pdht_hip_xpose64_plan_for; host arithmetic only).  cus = None: the CUs of
+    the current GPU; rounds_per_wg = -1: the library's own choice, 0: the
+    persistent shape; hist: a call that accumulates a histogram."""
+    if cus is None:
+        torch = _torch()
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    p = Xpose64Plan()
+    _check(lib().pdht_hip_xpose64_plan_for(n, cus, rounds_per_wg, int(hist), C.byref(p)), "pdht_hip_xpose64_plan_for")
+    return p
+
+
+def xpose64_tiles(plan: Xpose64Plan, block0: int = 0, nblocks: int = None) -> np.ndarray:
+    """Tile numbers of workgroups [block0, block0 + nblocks) of the plan's
+    (first) launch as a (nblocks, rounds, 2, 4) uint64 array indexed [workgroup,
+    its r-th round, d, wave], from the function the kernel indexes with."""
+    nblocks = plan.grid - block0 if nblocks is None else nblocks
+    rw = plan.rounds_per_wg if plan.round_blocked else plan.rounds
+    t = np.empty((nblocks, rw, 2, 4), dtype=np.uint64)
+    _check(lib().pdht_hip_xpose64_tiles(C.byref(plan), block0, nblocks, t.ctypes.data_as(C.c_void_p)),
+           "pdht_hip_xpose64_tiles")
+    return t
 
 
 def key_stream_var(data, offsets, out=None, stream=None, check=True):

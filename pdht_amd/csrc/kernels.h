@@ -546,19 +546,48 @@ __device__ __forceinline__ u32 xpose_slot(u32 k, u32 c) { return 4 * k + (c ^ ((
 // 4 contiguous 16-B pieces of the NEXT tile (global_load_dwordx4, 1 KiB per
 // wave-instruction) while the current tile hashes, then writes them into the
 // image with ds_write_b128.
+//
+// Tile order.  A "round" is DEPTH x W consecutive tiles, W = the waves the
+// persistent grid keeps resident: in round r, wave `wave` of the workgroup in
+// slot `slot` (of W / wpb) hashes tile xpose64_tile(..., r, d, slot, wave) for
+// d < DEPTH.  The persistent shape (R = 0) is one workgroup per slot walking
+// every round.  The round-blocked shape (R > 0) cuts the same order into
+// workgroups of R rounds each, workgroup b = slot b % (W / wpb) of round block
+// b / (W / wpb): the dispatcher hands workgroups out in blockIdx order, so the
+// tiles in flight stay within about R + 1 rounds of each other however
+// unevenly the waves are served.  launch.h's xpose64_plan sizes the grid from
+// this same function.
+__host__ __device__ __forceinline__ u64 xpose64_tile(u32 W, u32 depth, u32 wpb, u64 round, u32 d, u32 slot,
+                                                     u32 wave) {
+  return (round * depth + d) * W + (u64)wpb * slot + wave;
+}
+// static LDS of k_fixed_xpose64 (launch.h pads it to hold the workgroups per CU)
+template <class Sink, int BLOCK>
+constexpr size_t xpose64_static_lds() {
+  return (size_t)(BLOCK / 64) * 4096 + sizeof(u32) * Sink::kHist;
+}
+
 template <class Algo, class Sink, bool LNT = false, int DEPTH = 1, int BLOCK = kBlock, int PRIO = 0>
 __global__ __launch_bounds__(BLOCK) void k_fixed_xpose64(const uint8_t *__restrict__ keys, u64 n,
-                                                         Algo algo, Sink sink) {
+                                                         Algo algo, Sink sink, u32 W = 0, u32 R = 0) {
   constexpr int kWavesPerBlock = BLOCK / 64;
   __shared__ __attribute__((aligned(16))) u32x4 img[kWavesPerBlock][256];  // 4 KiB per wave
   __shared__ u32 lds_hist[Sink::kHist];
+  static_assert(sizeof(img) + sizeof(lds_hist) == xpose64_static_lds<Sink, BLOCK>(), "launch.h pads this");
   sink.lds_hist = lds_hist;
   sink.init();
   const u32 wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const u32 lane = threadIdx.x & 63;
   const u64 ntiles = (n + 63) >> 6;
   const u64 full = n >> 6;
-  const u64 nwaves = (u64)gridDim.x * kWavesPerBlock;
+  // R = 0: W is what this grid holds; R > 0: W comes from the plan
+  const u32 slots = R ? W / kWavesPerBlock : gridDim.x;
+  const u64 nwaves = (u64)slots * kWavesPerBlock;
+  const u32 q = R ? blockIdx.x / slots : 0;  // round block
+  const u32 slot = blockIdx.x - q * slots;
+  // this workgroup's tiles lie below `end`, its whole ones below `efull`
+  const u64 end = R ? min(ntiles, ((u64)q + 1) * R * DEPTH * nwaves) : ntiles;
+  const u64 efull = min(full, end);
   // DEPTH tiles of prefetch in flight per wave (register sets, static index)
   u32x4 pre[DEPTH][4];
   auto fetch = [&](int d, u64 t) {
@@ -566,15 +595,15 @@ __global__ __launch_bounds__(BLOCK) void k_fixed_xpose64(const uint8_t *__restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) pre[d][j] = ld<LNT>(src + 64 * j + lane);
   };
-  const u64 t0 = (u64)blockIdx.x * kWavesPerBlock + wave;
+  const u64 t0 = xpose64_tile((u32)nwaves, DEPTH, kWavesPerBlock, (u64)q * R, 0, slot, wave);
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d)
-    if (t0 + d * nwaves < full) fetch(d, t0 + d * nwaves);
-  for (u64 t = t0; t < ntiles; t += DEPTH * nwaves) {
+    if (t0 + d * nwaves < efull) fetch(d, t0 + d * nwaves);
+  for (u64 t = t0; t < end; t += DEPTH * nwaves) {
 #pragma unroll
     for (int d = 0; d < DEPTH; ++d) {
       const u64 tt = t + d * nwaves;
-      if (tt >= ntiles) break;  // wave-uniform
+      if (tt >= end) break;  // wave-uniform
       const u64 i = (tt << 6) + lane;
       RegReader<16> r;
       if (tt < full) {
@@ -588,7 +617,7 @@ __global__ __launch_bounds__(BLOCK) void k_fixed_xpose64(const uint8_t *__restri
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const u64 tn = tt + DEPTH * nwaves;
         if constexpr (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-        if (tn < full) fetch(d, tn);  // refill this register set while hashing
+        if (tn < efull) fetch(d, tn);  // refill this register set while hashing
         if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
         const u32 sw = (lane >> 2) & 3;
 #pragma unroll

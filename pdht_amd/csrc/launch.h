@@ -7,6 +7,16 @@
 namespace pdht {
 
 constexpr int kWinBytes = 12288;  // k_window over fixed keys: LDS window per wave (12 KiB)
+
+// Launch shape of k_fixed_xpose64<nt,d2> over a batch without a histogram:
+// R rounds per workgroup (kernels.h; 0 = the persistent grid, big batches
+// split into launches of kLaunchBytes) at `per_cu` workgroups per CU, held by
+// padding the workgroup's LDS (0 = whatever the kernel's resources admit).
+struct Xpose64Shape {
+  u32 R;
+  int per_cu;
+};
+constexpr int kXposeDepth = 2, kXposePerCu = 3;
 }  // namespace pdht
 // one A/B hook per launch path below (product/pdht_hooks_launch.h: none taken)
 #include "pdht_hooks_launch.h"
@@ -89,10 +99,13 @@ static bool sink_has_hist(const Sink &s) {
 // specialised lengths when the layout allows them, else the window kernel
 // (a 64-key tile fits 12 or 16 KiB of LDS), else per-lane global reads.
 // Batches larger than this many key bytes go out as consecutive launches of
-// about this size.  One persistent launch over a large batch streams slower
-// than the same keys in shorter launches: over a long launch the waves drift
-// apart and the memory the chip has in flight spreads over ever more of the
-// buffer.  Interleaved A/B (tools/abbench.py, r03), 64-B keys, ms per batch:
+// about this size -- every path but packed 64-B keys without a histogram,
+// which take ONE round-blocked launch (kXposeShape below).  One persistent
+// launch over a large batch streams slower than the same keys in shorter
+// launches: over a long launch the waves drift apart and the memory the chip
+// has in flight spreads over ever more of the buffer.  What the split bought
+// the PERSISTENT 64-B grid (still the shape of the histogram sinks);
+// interleaved A/B (tools/abbench.py, r03), 64-B keys, ms per batch:
 //   chunk               cfg5 128M keys (8 GiB)    cfg2 16M keys (1 GiB)
 //   one launch          1.806 (0.669)             0.2034 (0.742)
 //   4 GiB / 2 GiB       -     / 1.675             -
@@ -103,14 +116,104 @@ static bool sink_has_hist(const Sink &s) {
 constexpr u64 kLaunchBytes = 512ull << 20;
 static u64 launch_chunk_bytes() { return hook_chunk_bytes(kLaunchBytes); }
 
+// The product's shape of the 64-B kernel for sinks without a histogram: ONE
+// launch of one-round workgroups, 3 per CU.  The launch boundary of the split
+// above was serving as a barrier that pulls the drifting waves of a
+// persistent grid back into one window; workgroups of one round each, handed
+// out by the dispatcher in blockIdx order, keep the window compact without a
+// boundary (and without atomics: nothing waits on anything).  Interleaved A/B
+// (tools/abbench.py --pair, 7 rounds x 10; profiles/xpose_dispatch), ms per
+// batch, persistent grid in 512 MiB launches -> R = 1 / 2 / 4 / 8 / 16:
+//   cfg2 16M keys     0.1964 -> 0.1849 / 0.1888 / 0.1925 / 0.1944 / 0.1974
+//   cfg4 16M, Crc128  0.2268 -> 0.2031 / 0.2114 / 0.2172 / 0.2207 / 0.2257
+//   cfg5 128M keys    1.5726 -> 1.5111 / 1.5644 / 1.5627 / 1.6393 / 1.7217
+//   1M keys (2.7 rounds) 0.0165 -> 0.0169 / 0.0163 / 0.0164 / 0.0163 / 0.0163
+// (the 1M-key ranges overlap, 0.0163-0.0182 against 0.0163-0.0176: no gate);
+// 4 per CU and no LDS pad (5 per CU by registers) lose to 3 at every R.
+// Tuning 350-360 are these shapes, 361 the persistent grid in launches.
+constexpr Xpose64Shape kXposeShape = {1, kXposePerCu};
+
+// Plan of k_fixed_xpose64<nt,d2> (256 threads) over n packed 64-B keys on a
+// chip of `cus` CUs at R rounds per workgroup: W = the waves of the
+// persistent grid, one round = kXposeDepth x W tiles.  Round-blocked when the
+// batch spans more than R rounds (up to R the two shapes are the same
+// launch): ceil(rounds / R) round blocks of W / 4 workgroups, the last one
+// cut after its last workgroup that still has a tile.
+static pdht_hip_xpose64_plan xpose64_plan(u64 n, int cus, u32 R) {
+  pdht_hip_xpose64_plan p{};
+  const u64 ntiles = (n + 63) / 64;
+  const u64 slots = std::max<u64>(1, std::min<u64>((n + 255) / 256, (u64)std::max(1, cus) * kXposePerCu));
+  const u64 G = kXposeDepth * slots * kWavesPerBlock;
+  p.waves = (u32)(slots * kWavesPerBlock);
+  p.rounds = (ntiles + G - 1) / G;
+  p.grid = slots;
+  p.launches = n ? 1 : 0;
+  if (R && p.rounds > R) {
+    const u64 qlast = (p.rounds - 1) / R;
+    const u64 left = ntiles - qlast * R * G;  // tiles from the last round block's first on
+    const u64 grid = qlast * slots + std::min<u64>(slots, (left + kWavesPerBlock - 1) / kWavesPerBlock);
+    if (grid <= 0x7fffffffu) {
+      p.grid = grid;
+      p.rounds_per_wg = R;
+      p.round_blocked = 1;
+    }
+  }
+  return p;
+}
+
+// (the tag names the kernel and its workgroups per CU, as for every shape)
+static const char *xpose64_tag(Xpose64Shape s) {
+  return s.per_cu == 3 ? "k_fixed_xpose64<nt,d2>@3" : s.per_cu == 4 ? "k_fixed_xpose64<nt,d2>@4"
+                                                                    : "k_fixed_xpose64<nt,d2>@unpadded";
+}
+
+// LDS of a CU and the unit a workgroup's allocation is rounded up to
+constexpr size_t kCuLdsBytes = 160 * 1024, kLdsGranule = 1280;
+
+// One launch of the plan.  per_cu workgroups per CU are held by LDS: each
+// asks for the largest whole number of granules of which per_cu fit a CU (and
+// per_cu + 1 do not), the kernel's own static LDS counted in.
+template <class Algo, class SinkNt>
+static int launch_xpose64_plan(const uint8_t *k, u64 n, Algo algo, SinkNt snt, const pdht_hip_xpose64_plan &p,
+                               int per_cu, hipStream_t st) {
+  constexpr size_t fixed = xpose64_static_lds<SinkNt, kBlock>();
+  size_t dyn = 0;
+  if (per_cu > 0) {
+    const size_t total = kCuLdsBytes / per_cu / kLdsGranule * kLdsGranule;
+    if (total < fixed || total - fixed > 65536 || total * (per_cu + 1) <= kCuLdsBytes)
+      return fail("k_fixed_xpose64: no LDS size holds %s%lld workgroups per CU", "", per_cu);
+    dyn = total - fixed;
+  }
+  k_fixed_xpose64<Algo, SinkNt, true, kXposeDepth>
+      <<<(unsigned)p.grid, kBlock, dyn, st>>>(k, n, algo, snt, p.waves, p.rounds_per_wg);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 template <class Algo, class Sink>
 static int launch_fixed_one(const void *keys, size_t stride, size_t keylen, size_t n, Algo algo, Sink sink,
                             hipStream_t st);
 
-// Fixed-length keys in launches of about launch_chunk_bytes() each.
+// Fixed-length keys in launches of about launch_chunk_bytes() each; packed
+// 64-B keys without a histogram in ONE round-blocked launch when the shape
+// says so and the batch spans more rounds than a workgroup serves.
 template <class Algo, class Sink>
 static int launch_fixed(const void *keys, size_t stride, size_t keylen, size_t n, Algo algo, Sink sink,
                         hipStream_t st) {
+  if constexpr (!HasCrcLds<Algo>::value) {
+    const Xpose64Shape shape = hook_xpose64_shape(kXposeShape);
+    if (shape.R && keys && n && stride == 64 && keylen == 64 && ((uintptr_t)keys & 15) == 0 &&
+        !sink_has_hist(sink)) {
+      int dev;
+      if (int rc = current_device(&dev)) return rc;
+      const pdht_hip_xpose64_plan p = xpose64_plan(n, g_dev[dev].cus, shape.R);
+      if (p.round_blocked) {
+        g_kernel = xpose64_tag(shape);
+        return launch_xpose64_plan(static_cast<const uint8_t *>(keys), n, algo, NtSink<Sink>::make(sink), p,
+                                   shape.per_cu, st);
+      }
+    }
+  }
   const u64 per = std::max<u64>(1, launch_chunk_bytes() / std::max<u64>(stride, 1));
   // Keys too long for a 64-key window (k_global: per-lane walks, compute-
   // heavy) go out in ONE launch: every launch ends in a tail of idle CUs, and

@@ -6,6 +6,7 @@
 // batches) and pdht_bucket.hip (destination bucketing).  Kernels: kernels.h,
 // bucket.h.  Algorithm: city_core.h.
 #include "runtime.h"
+#include "launch.h"
 
 namespace pdht {
 
@@ -182,8 +183,9 @@ PDHT_API int pdht_hip_read_stream_dev(const void *buf, size_t bytes, int nt, uin
 }
 
 // Key-stream calibration: exactly the default 64-B kernel's data movement
-// (k_fixed_xpose64, nt loads and stores, same grid) with the hash replaced by
-// an XOR fold, so hash cost = kernel time - this time.
+// (k_fixed_xpose64, nt loads and stores, the same launch plan through the
+// same launch helper) with the hash replaced by an XOR fold, so hash cost =
+// kernel time - this time.
 PDHT_API int pdht_hip_key_stream_dev(const void *keys, size_t n, uint64_t *out,
                                      pdht_hip_stream_t s) {
   if (n == 0) return 0;
@@ -193,10 +195,49 @@ PDHT_API int pdht_hip_key_stream_dev(const void *keys, size_t n, uint64_t *out,
   Sink64T<true> sink{};
   sink.out = out;
   g_kernel = "k_fixed_xpose64<fold,nt,d2>@3";
+  const Xpose64Shape shape = hook_xpose64_shape(kXposeShape);
+  const pdht_hip_xpose64_plan p = xpose64_plan(n, g_dev[dev].cus, shape.R);
+  if (p.round_blocked)
+    return launch_xpose64_plan(static_cast<const uint8_t *>(keys), n, AlgoFold64{}, sink, p, shape.per_cu, ST(s));
   k_fixed_xpose64<AlgoFold64, Sink64T<true>, true, 2>
       <<<grid_for((n + 255) / 256, 3, dev), kBlock, 0, ST(s)>>>(static_cast<const uint8_t *>(keys), n,
                                                                 AlgoFold64{}, sink);
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The 64-B kernel's launch plan (host arithmetic only: launch.h's xpose64_plan
+// and the tile function the kernel indexes with, kernels.h)
+PDHT_API int pdht_hip_xpose64_plan_for(size_t n, int cus, int rounds_per_wg, int with_hist,
+                                       pdht_hip_xpose64_plan *plan) {
+  if (!plan || cus < 1) return fail("bad arguments%s", "");
+  const u32 R = with_hist ? 0 : rounds_per_wg < 0 ? hook_xpose64_shape(kXposeShape).R : (u32)rounds_per_wg;
+  *plan = xpose64_plan(n, cus, R);
+  if (!plan->round_blocked) {  // launch_fixed's split
+    const u64 per = std::max<u64>(1, launch_chunk_bytes() / 64);
+    const u64 step = (per + 4095) & ~(u64)4095;
+    if (n > per) {
+      *plan = xpose64_plan(step, cus, 0);
+      plan->launches = (n + step - 1) / step;
+    }
+  }
+  return 0;
+}
+
+PDHT_API int pdht_hip_xpose64_tiles(const pdht_hip_xpose64_plan *plan, uint64_t block0, size_t nblocks,
+                                    uint64_t *tiles) {
+  if (!plan || !tiles || plan->waves < kWavesPerBlock || block0 + nblocks > plan->grid)
+    return fail("bad arguments%s", "");
+  const u32 slots = plan->waves / kWavesPerBlock, R = plan->rounds_per_wg;
+  const u64 rw = plan->round_blocked ? R : plan->rounds;
+  for (u64 b = block0; b < block0 + nblocks; ++b) {
+    const u64 q = plan->round_blocked ? b / slots : 0;
+    const u32 slot = (u32)(b - q * slots);
+    for (u64 r = 0; r < rw; ++r)
+      for (u32 d = 0; d < (u32)kXposeDepth; ++d)
+        for (u32 w = 0; w < (u32)kWavesPerBlock; ++w)
+          *tiles++ = xpose64_tile(plan->waves, kXposeDepth, kWavesPerBlock, q * R + r, d, slot, w);
+  }
   return 0;
 }
 

@@ -25,6 +25,10 @@ extern "C" {
  *              80/81  1024-thread transpose at 1 / 2 WG/CU (cfg1 shape)
  *                 82  the 256-thread transpose whatever the histogram
  *            250/251  tile order scattered (bijection) / per-wave contiguous runs
+ *            350-354  ONE round-blocked launch, 1 / 2 / 4 / 8 / 16 rounds per workgroup, 3 WG/CU
+ *            355-357  the same at 1 / 2 / 4 rounds, 4 WG/CU
+ *            358-360  the same at 1 / 2 / 4 rounds, no LDS pad (occupancy by the kernel's resources)
+ *                361  the persistent grid in 512 MiB launches
  *   long keys     96  r02 spans before the 128-B line spans (240-B / 64-B)
  *                153  timing only: CRC lookups replaced by a fold (wrong digests)
  *                150  CRC-32C on r02's 6-bit-slice tables (product: byte tables)

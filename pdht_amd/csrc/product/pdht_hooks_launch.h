@@ -15,5 +15,6 @@ static inline int hook_long_walk(A &&...) { return kNoVariant; }
 template <class... A>
 static inline int hook_var(A &&...) { return kNoVariant; }
 static inline u64 hook_chunk_bytes(u64 dflt) { return dflt; }
+static inline Xpose64Shape hook_xpose64_shape(Xpose64Shape dflt) { return dflt; }
 
 }  // namespace pdht

@@ -9,7 +9,12 @@
 //                stores; 80 / 81 1024-thread transpose at 1 / 2 WG/CU; 82 the
 //                256-thread shape whatever the histogram; 188 digests stored
 //                16 B per lane; 206 s_setprio 1 around the prefetch issue;
-//                250 / 251 the tile order scattered / in per-wave runs
+//                250 / 251 the tile order scattered / in per-wave runs;
+//                350-354 one round-blocked launch, 1 / 2 / 4 / 8 / 16 rounds
+//                per workgroup at 3 WG/CU; 355-357 1 / 2 / 4 rounds at 4
+//                WG/CU; 358-360 1 / 2 / 4 rounds, occupancy left to the
+//                kernel's resources; 361 the persistent grid in 512 MiB
+//                launches
 //   small keys   219 / 220 8-B placement with 4 / 16 keys per lane in flight;
 //                221 8-B hashing with plain loads; 222 / 223 8 keys per lane
 //                (256 / 1024 threads); 224 32-B keys with plain loads and
@@ -100,6 +105,19 @@ static u64 hook_chunk_bytes(u64 dflt) {
     case 118: return ~0ull;
     default: return dflt;
   }
+}
+
+// packed, 16-B aligned 64-B keys without a histogram: rounds per workgroup and
+// workgroups per CU of the round-blocked shape.  Every other variant keeps
+// the persistent grid in launch_chunk_bytes() launches, which its own shape
+// (hook_xpose64, hook_chunk_bytes) was measured against.
+static Xpose64Shape hook_xpose64_shape(Xpose64Shape dflt) {
+  const int v = tuning_variant();
+  if (v == 0) return dflt;
+  if (v >= 350 && v <= 354) return {1u << (v - 350), 3};  // R = 1, 2, 4, 8, 16 at 3 WG/CU
+  if (v >= 355 && v <= 357) return {1u << (v - 355), 4};  // R = 1, 2, 4 at 4 WG/CU
+  if (v >= 358 && v <= 360) return {1u << (v - 358), 0};  // R = 1, 2, 4, no LDS pad
+  return {0, dflt.per_cu};                                // 361 and every other variant
 }
 
 // packed, 16-B aligned 64-B keys
