@@ -36,6 +36,7 @@ __all__ = [
     "device_count", "PdhtTable", "K2", "bucket_batch", "bucket_records", "record_fields",
     "bucket_record_bytes", "bucket_workspace_bytes", "WeakHashLen32WithSeeds", "WeakHashLen32WithSeeds6",
     "tuning", "last_kernel", "mpi_lib", "table_bytes", "table_reply_bytes", "DeviceTable", "get_resolve",
+    "table_export_workspace_bytes",
 ]
 
 K2 = 0x9AE16A3B2F90404F  # city.c:96 (CityHash64WithSeed's seed0)
@@ -136,6 +137,8 @@ def _declare(L, tuning=False):
         "pdht_table_reply_bytes": (C.c_size_t, [_S, _S]),
         "pdht_table_get_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _V]),
         "pdht_table_counts_dev": (C.c_int, [_V, _V, _V]),
+        "pdht_table_export_workspace_bytes": (C.c_size_t, [_U64]),
+        "pdht_table_export_dev": (C.c_int, [_V, _U64, _S, _U64, _U64, _V, _S, _V, _S, _V, _S, _U64, _V, _V, _S, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
@@ -905,6 +908,28 @@ def table_reply_bytes(head: int, rowbytes: int) -> int:
     return b
 
 
+def table_export_workspace_bytes(nslots: int) -> int:
+    """Bytes of workspace DeviceTable.export needs for a range of `nslots` slots
+    (1 .. capacity + 1); a function of nslots only."""
+    b = lib().pdht_table_export_workspace_bytes(nslots) if 0 < nslots <= (1 << 31) + 1 else 0
+    if b == 0:
+        raise ValueError(f"nslots {nslots} must be in 1 .. 2^31 + 1")
+    return b
+
+
+def _strided_1d(t, name, dtype, device):
+    """t: a 1-D CUDA tensor of `dtype` on `device`, dense or strided (a column
+    of a wider tensor) -> (entries, stride in bytes)."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or not t.is_cuda or t.device != device:
+        raise ValueError(f"{name} must be a 1-D {dtype} CUDA tensor on {device}")
+    m = t.shape[0]
+    stride = t.stride(0) * t.element_size() if m > 1 else t.element_size()
+    if stride < t.element_size():
+        raise ValueError(f"{name} must have a positive stride")
+    return m, stride
+
+
 class DeviceTable:
     """A target table in device memory: opaque rows of `rowbytes` bytes under
     64-bit mbits (include/pdht_hip_table.h).  For put records rowbytes is the
@@ -1024,6 +1049,145 @@ class DeviceTable:
         """(entries stored, records dropped, put batches applied, slots
         inspected by puts); the last three cumulative.  Host-synchronous."""
         return tuple(int(x) for x in self.counts_dev().cpu().tolist())
+
+    # ---- enumerate and grow (include/pdht_hip_table_iter.h) ----
+    def _slot_range(self, first_slot, nslots):
+        first_slot = int(first_slot)
+        nslots = self.capacity + 1 - first_slot if nslots is None else int(nslots)
+        if first_slot < 0 or nslots < 1 or first_slot + nslots > self.capacity + 1:
+            raise ValueError(f"slots [{first_slot}, {first_slot + nslots}) are not a non-empty range inside "
+                             f"0 .. {self.capacity + 1}")
+        return first_slot, nslots
+
+    def export(self, mbits, rows=None, slots=None, *, first_slot=0, nslots=None, count=None, workspace=None,
+               stream=None):
+        """The live slots of [first_slot, first_slot + nslots) (slots 0 ..
+        capacity, the last one mbits 0's private slot; nslots None = to the
+        end) in ascending slot order, asynchronously: entry e < len(mbits)
+        goes to mbits[e] (int64, 1-D), rows[e] (uint8 [m, rowbytes]) and
+        slots[e] (int32, 1-D); rows and slots may be None.  All three may be
+        row-strided views -- of one [m, stride] uint8 record buffer for the
+        record form (export_records).  Nothing else is written.  A tensor of 0
+        entries (or None) for mbits is the count-only form.  Returns the int64
+        [2] count tensor (`count`, allocated if None): live slots of the
+        range, entries written.  Page by resuming at slots[last] + 1.
+        workspace: uint8, >= table_export_workspace_bytes(nslots) bytes,
+        16-byte aligned (allocated if None); its contents are never read."""
+        torch = _torch()
+        first_slot, nslots = self._slot_range(first_slot, nslots)
+        m, mp, ms, rp, rs, sp, ss = 0, None, 8, None, 8, None, 4
+        if mbits is not None:
+            m, ms = _strided_1d(mbits, "mbits", torch.int64, self.device)
+        if m:
+            mp = mbits.data_ptr()
+            if ms % 8:
+                raise ValueError("mbits must have a byte stride that is a multiple of 8")
+            if rows is not None:
+                rm, rB, rs = _rows_2d(rows, "rows", self.device)
+                if (rm, rB) != (m, self.rowbytes):
+                    raise ValueError(f"rows must have shape [{m}, {self.rowbytes}], got {tuple(rows.shape)}")
+                if rs % 8 or rows.data_ptr() % 8:
+                    raise ValueError("rows must be 8-byte aligned with a row stride that is a multiple of 8")
+                rp = rows.data_ptr()
+            if slots is not None:
+                sm, ss = _strided_1d(slots, "slots", torch.int32, self.device)
+                if sm != m:
+                    raise ValueError(f"slots must have {m} entries, got {sm}")
+                sp = slots.data_ptr()
+        if count is None:
+            count = torch.empty(2, dtype=torch.int64, device=self.device)
+        _need(count, "count", torch.int64, self.device, shape=(2,))
+        need = table_export_workspace_bytes(nslots)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 16:
+                raise ValueError("workspace must be 16-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_export_dev(_dptr(self.storage), self.capacity, self.rowbytes, first_slot, nslots,
+                                               mp, ms, rp, rs, sp, ss, m, _dptr(count), _dptr(workspace),
+                                               workspace.numel(), g.stream), "pdht_table_export_dev")
+        return count
+
+    def export_records(self, records, *, first_slot=0, nslots=None, count=None, workspace=None, stream=None):
+        """export() in the record form: entry e becomes put record e of
+        `records` (uint8 [m, stride], 8-byte aligned, stride a multiple of 8
+        and >= 24 + rowbytes): slot index at +12, mbits at +16, row at +24;
+        bytes +0 .. +11 and the pad behind the row keep what they held.  The
+        first count[1] records feed put_records of another table as they
+        stand."""
+        torch = _torch()
+        m, S, stride = _rows_2d(records, "records", self.device)
+        if S < 24 + self.rowbytes:
+            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {S}")
+        if stride % 8 or records.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        if m == 0:
+            return self.export(None, first_slot=first_slot, nslots=nslots, count=count, workspace=workspace,
+                               stream=stream)
+        mb = records[:, 16:24].view(torch.int64)[:, 0]  # three views of the one buffer
+        sl = records[:, 12:16].view(torch.int32)[:, 0]
+        return self.export(mb, records[:, 24:24 + self.rowbytes], sl, first_slot=first_slot, nslots=nslots,
+                           count=count, workspace=workspace, stream=stream)
+
+    def entries(self, first_slot=0, nslots=None):
+        """The entries of a slot range in slot order, trimmed: (mbits int64
+        [e], rows uint8 [e, rowbytes], slots int32 [e]).  Host-synchronous
+        (it reads the count before it allocates), like counts()."""
+        torch = _torch()
+        first_slot, nslots = self._slot_range(first_slot, nslots)
+        ws = torch.empty(table_export_workspace_bytes(nslots), dtype=torch.uint8, device=self.device)
+        e = int(self.export(None, first_slot=first_slot, nslots=nslots, workspace=ws).cpu()[0])
+        mbits = torch.empty(e, dtype=torch.int64, device=self.device)
+        rows = torch.empty((e, self.rowbytes // 8), dtype=torch.int64, device=self.device).view(torch.uint8)
+        rows = rows.view(e, self.rowbytes)
+        slots = torch.empty(e, dtype=torch.int32, device=self.device)
+        if e:
+            self.export(mbits, rows, slots, first_slot=first_slot, nslots=nslots, workspace=ws)
+        return mbits, rows, slots
+
+    def rehash(self, capacity: int, storage=None, chunk_bytes: int = 256 << 20, stream=None):
+        """A new DeviceTable of `capacity` and the same rowbytes holding this
+        table's entries; this table is left untouched.  rehash = export as
+        records -> put_records: the slots are walked in ranges whose record
+        buffer stays within chunk_bytes, each exported with room for every
+        slot of the range (a chunk is never cut), and put with exactly the
+        count it returned.  put_records takes its m from the host, so this is
+        host-synchronous -- one count read per chunk -- and cannot be captured
+        into a graph.  Raises ValueError before anything is allocated when the
+        ordinary entries (all but mbits 0, which has its private slot on both
+        sides) exceed `capacity`.  The new table's counters: entries as here,
+        dropped 0, batches = the chunks that held an entry."""
+        torch = _torch()
+        capacity = int(capacity)
+        table_bytes(capacity, self.rowbytes)  # the geometry, before anything else
+        if chunk_bytes < 1:
+            raise ValueError("chunk_bytes must be >= 1")
+        entries = self.counts()[0]
+        if entries > capacity + 1:
+            raise ValueError(f"{entries} entries do not fit a capacity of {capacity}")
+        if entries == capacity + 1:  # fits only with mbits 0 among them
+            if int(self.export(None, first_slot=self.capacity, nslots=1).cpu()[0]) == 0:
+                raise ValueError(f"{entries} ordinary entries do not fit a capacity of {capacity}")
+        new = DeviceTable(capacity, self.rowbytes, self.device, storage=storage)
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+        S = 24 + self.rowbytes
+        per = max(1, min(self.capacity + 1, chunk_bytes // S))
+        records = torch.empty((per, S // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(per, S)
+        ws = torch.empty(table_export_workspace_bytes(per), dtype=torch.uint8, device=self.device)
+        pws = torch.empty(max(per, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        count = torch.empty(2, dtype=torch.int64, device=self.device)
+        for s0 in range(0, self.capacity + 1, per):
+            n = min(per, self.capacity + 1 - s0)
+            self.export_records(records[:n], first_slot=s0, nslots=n, count=count, workspace=ws, stream=stream)
+            if stream is not None:
+                stream.synchronize()
+            c = int(count.cpu()[1])
+            if c:
+                new.put_records(records[:c], status=False, workspace=pws, stream=stream)
+        return new
 
 
 def get_resolve(replies, keys, elemsize: int, *, head: int = 8, key_slot: int = 0, index=None, values=None,

@@ -116,6 +116,10 @@ extern "C" {
  *                     non-temporal stores
  *   table        340  get replies stored plain (product: non-temporal)
  *                341  put rows stored plain (product: non-temporal)
+ *                342  export outputs (mbits, slot indices, rows) stored non-temporally
+ *                     (product: plain)
+ *                343  export: the write pass reads the ballot masks the count pass saved
+ *                     in the workspace (1 bit per slot) instead of the tags again
  *   host          61  chunked copy pipeline instead of zero-copy on pinned buffers
  *   small keys   219  8-B placement with a histogram, 4 keys per lane (the shape
  *                     before late r04; product: 8); 220 16 keys per lane

@@ -31,5 +31,7 @@ static inline bool hook_rows_nt(bool dflt) { return dflt; }
 // pdht_table.hip: non-temporal stores of the get replies / of a put's rows
 static inline bool hook_table_reply_nt(bool dflt) { return dflt; }
 static inline bool hook_table_put_nt(bool dflt) { return dflt; }
+// pdht_table_iter.hip: non-temporal stores of an export's mbits, slot indices and rows
+static inline bool hook_table_export_nt(bool dflt) { return dflt; }
 
 }  // namespace pdht

@@ -30,24 +30,9 @@
 //   k_table_write  a lane group per record: the record that owns its slot's winner word
 //                  copies its row; every group writes its status; one lane advances counters[2].
 #pragma once
-#include "rows.h"
+#include "table_geom.h"
 
 namespace pdht {
-
-constexpr u64 kTableMix = 0x9E3779B97F4A7C15ull;  // 2^64 / golden ratio
-constexpr u32 kTableNoSlot = 0xFFFFFFFFu;         // workspace mark of a dropped record
-constexpr size_t kTableTagsAt = 64;
-
-struct TableGeom {
-  u64 *counters;
-  u64 *tags;
-  u64 *win;
-  uint8_t *rows;
-  u64 mask;   // C - 1
-  u32 shift;  // 64 - log2 C
-  u32 cap;    // C (<= 2^31): the private slot's index
-  u64 rowbytes;
-};
 
 __device__ __forceinline__ u64 tag_load(const u64 *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -40,5 +40,7 @@ static inline bool hook_rows_nt(bool dflt) { return tuning_variant() == 330 ? !d
 // 340 / 341: the table's get replies / put rows stored in the other policy
 static inline bool hook_table_reply_nt(bool dflt) { return tuning_variant() == 340 ? !dflt : dflt; }
 static inline bool hook_table_put_nt(bool dflt) { return tuning_variant() == 341 ? !dflt : dflt; }
+// 342: the table export's outputs stored in the other policy
+static inline bool hook_table_export_nt(bool dflt) { return tuning_variant() == 342 ? !dflt : dflt; }
 
 }  // namespace pdht
