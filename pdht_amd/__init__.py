@@ -139,6 +139,10 @@ def _declare(L, tuning=False):
         "pdht_table_counts_dev": (C.c_int, [_V, _V, _V]),
         "pdht_table_export_workspace_bytes": (C.c_size_t, [_U64]),
         "pdht_table_export_dev": (C.c_int, [_V, _U64, _S, _U64, _U64, _V, _S, _V, _S, _V, _S, _U64, _V, _V, _S, _V]),
+        "pdht_table_update_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_update_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _V, _V]),
+        "pdht_table_cswap_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_cswap_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _S, _U64, _U64, _V, _S, _V, _S, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
@@ -889,6 +893,10 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   put: bucket_put_records -> dist.exchange_records -> DeviceTable.put_records
 #   get: bucket_records(msg_type=get) -> dist.exchange_records -> DeviceTable.get
 #        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
+#   update: bucket_put_records -> dist.exchange_records -> DeviceTable.update_records
+#   claim: bucket_records -> dist.exchange_records -> DeviceTable.cswap
+#        -> dist.exchange_replies -> scatter_rows(replies, index)
+#   (include/pdht_hip_table_rmw.h: pdht_update, pdht_atomic_cswap)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -975,6 +983,18 @@ class DeviceTable:
         later record of the batch / 2 dropped, table full), a uint8 [m] tensor
         = fill and return it, False / None = none.  workspace: uint8, >= 4*m
         bytes (allocated if None)."""
+        return self._apply_records("put", records, status, workspace, stream)
+
+    def update_records(self, records, status=True, workspace=None, stream=None):
+        """Applies a batch of put records as pdht_update would one after the
+        other (libpdht/putget.c:278; pdht_table_update_records_dev): find by
+        mbits, overwrite the row if the entry is there, do nothing otherwise.
+        Arguments as put_records.  status: 0 stored / 1 superseded by a later
+        record of the batch / 3 not found.  Nothing is ever inserted or
+        dropped; counts()[2] advances by one."""
+        return self._apply_records("update", records, status, workspace, stream)
+
+    def _apply_records(self, kind, records, status, workspace, stream):
         torch = _torch()
         m, B, stride = _rows_2d(records, "records", self.device)
         if B < 24 + self.rowbytes:
@@ -987,7 +1007,7 @@ class DeviceTable:
             status = None
         else:
             _need(status, "status", torch.uint8, self.device, shape=(m,))
-        need = lib().pdht_table_put_workspace_bytes(m)
+        need = getattr(lib(), f"pdht_table_{kind}_workspace_bytes")(m)
         if workspace is None:
             workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
         else:
@@ -995,10 +1015,9 @@ class DeviceTable:
             if workspace.data_ptr() % 4:
                 raise ValueError("workspace must be 4-byte aligned")
         with _on(self.device, stream) as g:
-            _check(lib().pdht_table_put_records_dev(_dptr(self.storage), self.capacity, self.rowbytes,
-                                                    _dptr(records), stride, m, _dptr(workspace),
-                                                    workspace.numel(), _opt(status), g.stream),
-                   "pdht_table_put_records_dev")
+            name = f"pdht_table_{kind}_records_dev"
+            _check(getattr(lib(), name)(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records), stride, m,
+                                        _dptr(workspace), workspace.numel(), _opt(status), g.stream), name)
         return status
 
     def get(self, mbits_or_records, head: int = 8, out=None, stream=None):
@@ -1010,20 +1029,8 @@ class DeviceTable:
         [m, head + rowbytes] tensor or row-strided view at any address; bytes
         outside its rows are not written."""
         torch = _torch()
-        t = mbits_or_records
         rb = table_reply_bytes(head, self.rowbytes)
-        if isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int64:
-            _need(t, "mbits", torch.int64, self.device)
-            m, ptr, stride = t.numel(), t.data_ptr(), 8
-        elif isinstance(t, torch.Tensor) and t.dim() == 2 and t.dtype == torch.uint8:
-            m, B, stride = _rows_2d(t, "records", self.device)
-            if B < 24:
-                raise ValueError(f"records must have >= 24 bytes per row, got {B}")
-            if stride % 8 or t.data_ptr() % 8:
-                raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
-            ptr = t.data_ptr() + 16
-        else:
-            raise ValueError("expected a 1-D int64 tensor of mbits or a 2-D uint8 record batch")
+        m, ptr, stride = self._requests(mbits_or_records)
         if out is None:
             out = torch.empty((m, rb // 8 if head == 8 else rb), dtype=torch.int64 if head == 8 else torch.uint8,
                               device=self.device).view(torch.uint8).view(m, rb)
@@ -1033,6 +1040,68 @@ class DeviceTable:
         with _on(self.device, stream) as g:
             _check(lib().pdht_table_get_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
                                             stride, m, _dptr(out), ostride, head, g.stream), "pdht_table_get_dev")
+        return out
+
+    def _requests(self, t):
+        """(m, address of the first mbits, stride) of a batch of requests: a
+        1-D int64 tensor of dense mbits, or a 2-D uint8 record batch read in
+        place at +16."""
+        torch = _torch()
+        if isinstance(t, torch.Tensor) and t.dim() == 1 and t.dtype == torch.int64:
+            _need(t, "mbits", torch.int64, self.device)
+            return t.numel(), t.data_ptr(), 8
+        if isinstance(t, torch.Tensor) and t.dim() == 2 and t.dtype == torch.uint8:
+            m, B, stride = _rows_2d(t, "records", self.device)
+            if B < 24:
+                raise ValueError(f"records must have >= 24 bytes per row, got {B}")
+            if stride % 8 or t.data_ptr() % 8:
+                raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+            return m, t.data_ptr() + 16, stride
+        raise ValueError("expected a 1-D int64 tensor of mbits or a 2-D uint8 record batch")
+
+    def cswap(self, mbits_or_records, word_offset: int, compare: int, desired: int, out=None, workspace=None,
+              stream=None):
+        """Compare-and-swap of the uint64 at `word_offset` of the row of every
+        request, as pdht_atomic_cswap would one request after the other
+        (libpdht/atomics.c:81-154; pdht_table_cswap_dev): old = word; if word
+        == compare: word = desired.  Requests as in get (dense int64 mbits, or
+        records read in place at +16).  compare / desired: one pair per call,
+        any int in [-2^63, 2^64), passed as its 64-bit pattern.  Returns the
+        replies, uint8 [m, 16]: byte 0 = 1 found / 0 not found, bytes 1..7
+        zero, bytes 8..15 the old word (0 when not found) -- a head-8 get
+        reply of an 8-byte row, for dist.exchange_replies and scatter_rows.
+        Among the requests of one mbits only the first can see `compare`.
+        Nothing is inserted.  out: a uint8 [m, 16] tensor or row-strided view,
+        8-byte aligned with a stride that is a multiple of 8; workspace:
+        uint8, >= 4*m bytes (allocated if None)."""
+        torch = _torch()
+        m, ptr, stride = self._requests(mbits_or_records)
+        if not isinstance(word_offset, int) or word_offset < 0 or word_offset % 8 or \
+                word_offset + 8 > self.rowbytes:
+            raise ValueError(f"word_offset must be a multiple of 8 in 0 .. {self.rowbytes - 8}, got {word_offset}")
+        pair = []
+        for name, v in (("compare", compare), ("desired", desired)):
+            if not isinstance(v, int) or isinstance(v, bool) or not -(1 << 63) <= v < (1 << 64):
+                raise ValueError(f"{name} must be an int in [-2^63, 2^64), got {v!r}")
+            pair.append(v & ((1 << 64) - 1))
+        if out is None:
+            out = torch.empty((m, 2), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, 16)
+        om, oB, ostride = _rows_2d(out, "out", self.device)
+        if (om, oB) != (m, 16):
+            raise ValueError(f"out must have shape [{m}, 16], got {tuple(out.shape)}")
+        if ostride % 8 or out.data_ptr() % 8:
+            raise ValueError("out must be 8-byte aligned with a row stride that is a multiple of 8")
+        need = lib().pdht_table_cswap_workspace_bytes(m)
+        if workspace is None:
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 4:
+                raise ValueError("workspace must be 4-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_cswap_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
+                                              stride, m, word_offset, pair[0], pair[1], _dptr(out), ostride,
+                                              _dptr(workspace), workspace.numel(), g.stream), "pdht_table_cswap_dev")
         return out
 
     def counts_dev(self, out=None, stream=None):
@@ -1046,8 +1115,9 @@ class DeviceTable:
         return out
 
     def counts(self):
-        """(entries stored, records dropped, put batches applied, slots
-        inspected by puts); the last three cumulative.  Host-synchronous."""
+        """(entries stored, records dropped, batches applied -- put, update
+        and cswap --, slots inspected by puts); the last three cumulative.
+        Host-synchronous."""
         return tuple(int(x) for x in self.counts_dev().cpu().tolist())
 
     # ---- enumerate and grow (include/pdht_hip_table_iter.h) ----

@@ -6,10 +6,6 @@
 
 namespace pdht {
 
-// Store policy of the get replies and of a put's rows (EXPERIMENTS.md §R9: measured per rowbytes)
-constexpr bool kTableReplyNt = true;
-constexpr bool kTablePutNt = true;
-
 static thread_local char g_table_pair[96];
 
 static int table_put(void *table, u64 capacity, size_t rowbytes, const void *records, size_t record_stride,
@@ -46,6 +42,7 @@ static int table_put(void *table, u64 capacity, size_t rowbytes, const void *rec
   w.status = status;
   w.np = (u32)(rowbytes / (p16 ? 16 : 8));
   w.gshift = group_shift(w.np);
+  w.absent = 2;
   const unsigned grid = table_grid(m, (u64)(64u >> w.gshift) * kRowsInFlight, dev);
   const bool nt = hook_table_put_nt(kTablePutNt);
   if (p16)

@@ -65,7 +65,8 @@ struct ClaimArgs {
   u32 *slots;
 };
 
-__global__ __launch_bounds__(kBlock) void k_table_claim(const ClaimArgs a) {
+// (static: table.h is part of two translation units, pdht_table.hip and pdht_table_rmw.hip)
+static __global__ __launch_bounds__(kBlock) void k_table_claim(const ClaimArgs a) {
   const TableGeom &t = a.t;
   const u64 batch = t.counters[2] << 32;  // (only k_table_write of the same call, behind this kernel, writes it)
   const u64 nthreads = (u64)gridDim.x * kBlock;
@@ -122,6 +123,7 @@ struct WriteArgs {
   uint8_t *status;  // may be null
   u32 np;           // pieces of a row
   u32 gshift;       // log2 of the lane group (G = the power of two >= np, at most 64)
+  u32 absent;       // status of a record without a slot: 2 dropped (put), 3 not found (update, table_rmw.h)
 };
 
 // P: 16 or 8 bytes per piece.  Shape of k_rows: a group's loads (slot, winner word, row piece) of
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void k_table_write(const WriteArgs a) {
         for (u32 c = l + 64; c < a.np; c += 64)
           st<NT>(*reinterpret_cast<const T *>(s + (u64)c * P), reinterpret_cast<T *>(d + (u64)c * P));
       }
-      if (a.status && l == 0 && row[r] < a.m) a.status[row[r]] = slot[r] == kTableNoSlot ? 2 : own[r] ? 0 : 1;
+      if (a.status && l == 0 && row[r] < a.m) a.status[row[r]] = slot[r] == kTableNoSlot ? a.absent : own[r] ? 0 : 1;
     }
   }
 }

@@ -1,10 +1,16 @@
 // table_host.h -- host-side geometry of the device-resident target table, shared by its translation
-// units (pdht_table.hip: put, get, resolve; pdht_table_iter.hip: export): the geometry checks, the
-// layout of the caller's buffer as pointers, and the launch arithmetic of the lane-group kernels.
+// units (pdht_table.hip: put, get, resolve; pdht_table_rmw.hip: update, compare-and-swap;
+// pdht_table_iter.hip: export): the geometry checks, the layout of the caller's buffer as pointers, and
+// the launch arithmetic of the lane-group kernels.
 #pragma once
 #include "table_geom.h"
 
 namespace pdht {
+
+// Store policy of the get replies and of a put's rows (EXPERIMENTS.md §R9: measured per rowbytes); the
+// replies of a compare-and-swap and the rows of an update follow them (pdht_table_rmw.hip)
+constexpr bool kTableReplyNt = true;
+constexpr bool kTablePutNt = true;
 
 static bool geom_ok(u64 capacity, size_t rowbytes) {
   return capacity >= 64 && capacity <= (1ull << 31) && (capacity & (capacity - 1)) == 0 && rowbytes != 0 &&
