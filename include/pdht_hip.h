@@ -210,6 +210,12 @@ int pdht_hip_read_stream_dev(const void *buf, size_t bytes, int nt, uint64_t *ou
  * CityHash64 kernel moves them (same loads, LDS transpose, stores, grid).
  * The hash kernel's time minus this one is what the hash arithmetic costs. */
 int pdht_hip_key_stream_dev(const void *keys, size_t n, uint64_t *out, pdht_hip_stream_t stream);
+/* out[i] = values[i] % divisor, computed by the FastMod object the placement
+ * and bucketing kernels use (make_fastmod + FastMod::mod); divisor >= 1.
+ * values (device, 8-byte aligned) and out (device, 4-byte aligned) hold n
+ * entries; divisor 0, or a null pointer with n > 0, is refused. */
+int pdht_hip_mod_dev(const uint64_t *values, size_t n, uint32_t divisor,
+                     uint32_t *out, pdht_hip_stream_t stream);
 /* The same for offset-indexed keys: the variable-length kernel's window DMA,
  * offsets reads, LDS reads of every key byte and digest stores, with the hash
  * replaced by an XOR fold (out[i] = fold of key i; see tests). */

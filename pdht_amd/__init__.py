@@ -118,6 +118,7 @@ def _declare(L, tuning=False):
         "pdht_hip_read_stream_dev": (C.c_int, [_V, _S, C.c_int, _V, _V]),
         "pdht_hip_key_stream_dev": (C.c_int, [_V, _S, _V, _V]),
         "pdht_hip_key_stream_var_dev": (C.c_int, [_V, _S, _V, _S, _V, _V]),
+        "pdht_hip_mod_dev": (C.c_int, [_V, _S, _U32, _V, _V]),
         "pdht_hip_xpose64_plan_for": (C.c_int, [_S, C.c_int, C.c_int, C.c_int, C.POINTER(Xpose64Plan)]),
         "pdht_hip_xpose64_tiles": (C.c_int, [C.POINTER(Xpose64Plan), _U64, _S, _V]),
         "pdht_bucket_workspace_bytes": (C.c_size_t, [_S, _S, _U32]),
@@ -1348,6 +1349,28 @@ def key_stream(keys, out=None, stream=None):
     out = _out(n, 1, keys.device, out)
     with _on(keys.device, stream) as g:
         _check(lib().pdht_hip_key_stream_dev(_dptr(keys), n, _dptr(out), g.stream), "pdht_hip_key_stream_dev")
+    return out
+
+
+def mod_batch(values, divisor: int, out=None, stream=None):
+    """Calibration: values int64 [n] (bit patterns of u64, CUDA) -> int32 [n]
+    (bit patterns of u32), values[i] % divisor through the FastMod object of
+    the placement and bucketing kernels (pdht_hip_mod_dev).  divisor: 1 ..
+    2^32 - 1."""
+    torch = _torch()
+    if not isinstance(values, torch.Tensor) or values.dim() != 1 or not values.is_cuda:
+        raise ValueError("values must be a 1-D CUDA int64 tensor")
+    dev = values.device
+    _need(values, "values", torch.int64, dev)
+    if not 1 <= divisor <= 0xFFFFFFFF:
+        raise ValueError(f"divisor {divisor} must be in 1 .. 2^32 - 1")
+    n = values.numel()
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    else:
+        _need(out, "out", torch.int32, dev, shape=(n,))
+    with _on(dev, stream) as g:
+        _check(lib().pdht_hip_mod_dev(_dptr(values), n, divisor, _dptr(out), g.stream), "pdht_hip_mod_dev")
     return out
 
 

@@ -206,6 +206,31 @@ PDHT_API int pdht_hip_key_stream_dev(const void *keys, size_t n, uint64_t *out,
   return 0;
 }
 
+// Modulus calibration: nothing but the FastMod object the placement and
+// bucketing kernels carry (make_fastmod on the host, FastMod::mod per value),
+// so a test can hand it dividends of its choice instead of digests.
+namespace pdht {
+__global__ __launch_bounds__(kBlock) void k_fastmod(const u64 *__restrict__ values, u64 n, FastMod f,
+                                                    u32 *__restrict__ out) {
+  const u64 stride = (u64)gridDim.x * kBlock;
+  for (u64 i = (u64)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) out[i] = (u32)f.mod(values[i]);
+}
+}  // namespace pdht
+
+PDHT_API int pdht_hip_mod_dev(const uint64_t *values, size_t n, uint32_t divisor, uint32_t *out,
+                              pdht_hip_stream_t s) {
+  if (divisor == 0) return fail("divisor must be >= 1%s", "");
+  if (n == 0) return 0;
+  if (!values || !out) return fail("null values or out%s", "");
+  if (((uintptr_t)values & 7) || ((uintptr_t)out & 3)) return fail("misaligned values or out%s", "");
+  int dev;
+  if (int rc = current_device(&dev)) return rc;
+  g_kernel = "k_fastmod";
+  k_fastmod<<<grid_for((n + kBlock - 1) / kBlock, 8, dev), kBlock, 0, ST(s)>>>(values, n, make_fastmod(divisor), out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // The 64-B kernel's launch plan (host arithmetic only: launch.h's xpose64_plan
 // and the tile function the kernel indexes with, kernels.h)
 PDHT_API int pdht_hip_xpose64_plan_for(size_t n, int cus, int rounds_per_wg, int with_hist,
