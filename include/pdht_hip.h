@@ -234,6 +234,8 @@ int pdht_hip_key_stream_var_dev(const void *bytes, size_t nbytes, const uint64_t
 #include "pdht_hip_table_iter.h"
 /* Update and compare-and-swap on the table's entries. */
 #include "pdht_hip_table_rmw.h"
+/* The associative accumulate (pdht_acc) on the table's entries. */
+#include "pdht_hip_table_acc.h"
 /* The 64-B kernel's launch plan and tile order (host arithmetic). */
 #include "pdht_hip_plan.h"
 

@@ -144,6 +144,9 @@ def _declare(L, tuning=False):
         "pdht_table_update_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _V, _V]),
         "pdht_table_cswap_workspace_bytes": (C.c_size_t, [_S]),
         "pdht_table_cswap_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _S, _U64, _U64, _V, _S, _V, _S, _V]),
+        "pdht_table_acc_workspace_bytes": (C.c_size_t, [_S, C.c_uint]),
+        "pdht_table_acc_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, C.c_int, C.c_int, _S, _S, C.c_uint, _V, _S,
+                                                 _V, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
@@ -898,6 +901,8 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   claim: bucket_records -> dist.exchange_records -> DeviceTable.cswap
 #        -> dist.exchange_replies -> scatter_rows(replies, index)
 #   (include/pdht_hip_table_rmw.h: pdht_update, pdht_atomic_cswap)
+#   accumulate: bucket_put_records -> dist.exchange_records -> DeviceTable.acc_records
+#   (include/pdht_hip_table_acc.h: pdht_acc)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -924,6 +929,29 @@ def table_export_workspace_bytes(nslots: int) -> int:
     if b == 0:
         raise ValueError(f"nslots {nslots} must be in 1 .. 2^31 + 1")
     return b
+
+
+# pdht_acc's datatypes, operation and flag (include/pdht_hip_table_acc.h; the reference's enums)
+PDHT_ACC_INT32, PDHT_ACC_INT64, PDHT_ACC_DOUBLE = 0, 1, 2
+PDHT_ACC_ADD = 0
+PDHT_ACC_INSERT = 1
+
+
+def table_acc_workspace_bytes(m: int, insert: bool = False) -> int:
+    """Bytes of workspace DeviceTable.acc_records needs for m records: 0
+    without insert, 4*m + m rounded up to 4 with it."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_acc_workspace_bytes(m, PDHT_ACC_INSERT if insert else 0)
+
+
+def _acc_datatype(dtype):
+    torch = _torch()
+    kinds = {torch.int32: (PDHT_ACC_INT32, 4), torch.int64: (PDHT_ACC_INT64, 8),
+             torch.float64: (PDHT_ACC_DOUBLE, 8)}
+    if dtype not in kinds:
+        raise ValueError(f"dtype must be torch.int32, torch.int64 or torch.float64, got {dtype!r}")
+    return kinds[dtype]
 
 
 def _strided_1d(t, name, dtype, device):
@@ -1019,6 +1047,60 @@ class DeviceTable:
             name = f"pdht_table_{kind}_records_dev"
             _check(getattr(lib(), name)(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records), stride, m,
                                         _dptr(workspace), workspace.numel(), _opt(status), g.stream), name)
+        return status
+
+    def acc_records(self, records, dtype, value_offset: int, elems: int = 1, insert: bool = False, status=True,
+                    workspace=None, stream=None):
+        """Applies a batch of put records as pdht_acc would one after the
+        other (libpdht/pdht.h:349, AssocOpAdd; pdht_table_acc_records_dev):
+        find by mbits and add the `elems` elements of `dtype` (torch.int32,
+        torch.int64 or torch.float64) at `value_offset` of the record's row
+        into the same place of the entry's row; no other byte of a present
+        entry changes.  value_offset: a multiple of the element size, the
+        region inside the row.  insert=False: an absent mbits stays absent
+        (status 3) and no counter moves.  insert=True: an absent mbits is
+        created with the whole row of its first record in the batch, later
+        records of it add; a new mbits without a free slot is dropped
+        (status 2) as by put_records, and counts() advance as for a put.
+        status: 0 added / 2 dropped / 3 not found (True, a uint8 [m] tensor,
+        or False / None as in put_records).  Integers wrap and the result is
+        byte-exact; float64 sums are added in an order the schedule picks
+        (within n*u/(1 - n*u) * sum|x_i| of the exact sum, u = 2^-53), and
+        the table must be in ordinary device memory.  workspace: uint8, >=
+        table_acc_workspace_bytes(m, insert) bytes (allocated if None)."""
+        torch = _torch()
+        datatype, size = _acc_datatype(dtype)
+        for name, v in (("value_offset", value_offset), ("elems", elems)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+        if value_offset % size or elems < 1 or value_offset + elems * size > self.rowbytes:
+            raise ValueError(f"the region must be elems >= 1 elements of {size} bytes at a value_offset that is a "
+                             f"multiple of {size}, inside the {self.rowbytes}-byte row; got value_offset "
+                             f"{value_offset}, elems {elems}")
+        m, B, stride = _rows_2d(records, "records", self.device)
+        if B < 24 + self.rowbytes:
+            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
+        if stride % 8 or records.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        if status is True:
+            status = torch.empty(m, dtype=torch.uint8, device=self.device)
+        elif status is False or status is None:
+            status = None
+        else:
+            _need(status, "status", torch.uint8, self.device, shape=(m,))
+        flags = PDHT_ACC_INSERT if insert else 0
+        need = lib().pdht_table_acc_workspace_bytes(m, flags)
+        if workspace is None:
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 4:
+                raise ValueError("workspace must be 4-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_acc_records_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records),
+                                                    stride, m, datatype, PDHT_ACC_ADD, value_offset, elems, flags,
+                                                    _dptr(workspace), workspace.numel(), _opt(status), g.stream),
+                   "pdht_table_acc_records_dev")
         return status
 
     def get(self, mbits_or_records, head: int = 8, out=None, stream=None):

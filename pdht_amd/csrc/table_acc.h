@@ -1,0 +1,232 @@
+// table_acc.h -- the associative accumulate on the device-resident target table
+// (include/pdht_hip_table_acc.h; layout and probes: table.h): pdht_acc (libpdht/pdht.h:349, a stub in
+// libpdht/assoc.c:26-29) as one batch whose result is that of its records applied one after the other
+// in position order -- "find the entry, add to `elems` words of its row".
+//
+//   flags 0   k_table_acc<T>          a lane group per record: table_find, then device-scope atomic adds
+//                                     of the record's region into the row's, then the status byte.
+//                                     No winner words, no counters: one kernel.
+//   INSERT    k_table_acc_claim       one lane per record: k_table_claim's probe and counters; the
+//                                     winner word takes the FIRST position (0xFFFFFFFF - p, as
+//                                     k_table_locate<first>); the lane whose CAS created the tag marks
+//                                     its record as the creator and zeroes the region of the new row
+//                                     (no other lane touches that row in this kernel).
+//             k_table_acc<T, insert>  every record with a slot adds as above; the creator's group reads
+//                                     the winner word -- the first record f of the slot -- and copies the
+//                                     row bytes OUTSIDE the region from record f: disjoint from the
+//                                     atomics, so nothing races.  One lane advances counters[2].
+//   The kernel boundary is the only synchronisation: nothing spins, polls or waits on another lane.
+//
+// Integer sums wrap (unsigned arithmetic throughout), so any order of the adds gives the sequential
+// result.  Double sums depend on the order the schedule picks (pdht_hip_table_acc.h has the bound).
+//
+// Lanes of a wave whose records found the same slot add their addends together first and post one
+// atomic per element between them -- k_table_locate's leader scheme with a sum in place of the
+// maximum: a hot mbits would otherwise queue one atomic per record on one word.
+#pragma once
+#include "table_rmw.h"
+
+namespace pdht {
+
+template <class T>
+struct AccWord;  // the integer of T's size that moves T's bytes unchanged
+template <>
+struct AccWord<u32> {
+  typedef u32 type;
+};
+template <>
+struct AccWord<u64> {
+  typedef u64 type;
+};
+template <>
+struct AccWord<double> {
+  typedef u64 type;
+};
+
+// device-scope, no return value used: one global atomic add instruction each (fp64: -munsafe-fp-atomics)
+__device__ __forceinline__ void acc_add(u32 *p, u32 v) { atomicAdd(p, v); }
+__device__ __forceinline__ void acc_add(u64 *p, u64 v) {
+  atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+}
+__device__ __forceinline__ void acc_add(double *p, double v) { atomicAdd(p, v); }
+
+// What a lane without an addend feeds the in-wave sums: x + neutral == x bit for bit.  For doubles that is
+// -0.0 (x + +0.0 would turn a sum of -0.0s into +0.0).
+template <class T>
+__device__ __forceinline__ T acc_neutral() {
+  if constexpr (sizeof(T) == 8 && !std::is_integral<T>::value)
+    return -0.0;
+  else
+    return T(0);
+}
+
+__device__ __forceinline__ u32 acc_shfl_xor(u32 v, int o) { return (u32)__shfl_xor((int)v, o); }
+__device__ __forceinline__ u64 acc_shfl_xor(u64 v, int o) {
+  return (u64)__shfl_xor((unsigned long long)v, o);
+}
+__device__ __forceinline__ double acc_shfl_xor(double v, int o) { return __shfl_xor(v, o); }
+
+struct AccClaimArgs {
+  TableGeom t;
+  const uint8_t *records;
+  u64 record_stride;
+  u64 m;
+  u32 *slots;
+  uint8_t *creator;  // 1: this record's CAS created its slot's tag
+  u64 value_offset;  // of the region inside a row (a multiple of 4)
+  u64 region_words;  // its length in 32-bit words
+};
+
+static __global__ __launch_bounds__(kBlock) void k_table_acc_claim(const AccClaimArgs a) {
+  const TableGeom &t = a.t;
+  const u64 batch = t.counters[2] << 32;  // (only k_table_acc of the same call, behind this kernel, writes it)
+  const u32 lane = threadIdx.x & 63;
+  const u64 nthreads = (u64)gridDim.x * kBlock;
+  const u64 rounds = (a.m + nthreads - 1) / nthreads;  // whole waves stay together for the wave-wide steps
+  u32 n_new = 0, n_drop = 0, n_seen = 0;
+  u64 p = (u64)blockIdx.x * kBlock + threadIdx.x;
+  for (u64 r = 0; r < rounds; ++r, p += nthreads) {
+    u32 slot = kTableNoSlot;
+    if (p < a.m) {
+      const u64 mb = *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16);
+      bool made = false;
+      if (mb == 0) {
+        ++n_seen;
+        slot = t.cap;
+        made = tag_load(t.tags + t.cap) == 0 && atomicCAS((unsigned long long *)(t.tags + t.cap), 0ull, 1ull) == 0;
+      } else {
+        u64 h = (mb * kTableMix) >> t.shift;
+        for (u64 left = t.mask + 1; left; --left) {
+          h &= t.mask;
+          ++n_seen;
+          u64 tag = tag_load(t.tags + h);
+          if (tag == 0) {
+            tag = atomicCAS((unsigned long long *)(t.tags + h), 0ull, (unsigned long long)mb);
+            if (tag == 0) {
+              made = true;
+              tag = mb;
+            }
+          }
+          if (tag == mb) {
+            slot = (u32)h;
+            break;
+          }
+          ++h;
+        }
+        if (slot == kTableNoSlot) ++n_drop;
+      }
+      n_new += made;
+      a.slots[p] = slot;
+      a.creator[p] = made;
+      if (made) {  // the sums of a new entry start from zero: every record of it adds, the first included
+        u32 *z = reinterpret_cast<u32 *>(t.rows + (u64)slot * t.rowbytes + a.value_offset);
+        for (u64 c = 0; c < a.region_words; ++c) z[c] = 0;
+      }
+    }
+    // the first position into the winner word, one atomicMax per slot and wave where lanes share a slot
+    // (k_table_locate<true>'s scheme)
+    const u32 rank = 0xFFFFFFFFu - (u32)p;
+    bool todo = slot != kTableNoSlot, cand = todo;
+#pragma unroll
+    for (int k = 0; k < kLocateLeaders; ++k) {
+      const u64 open = __ballot(cand);
+      if (!open) break;  // (wave-uniform)
+      const u32 leader = (u32)__ffsll((unsigned long long)open) - 1;
+      const u32 s = (u32)__shfl((int)slot, (int)leader);
+      const bool mine = cand && slot == s;
+      cand = cand && !mine;
+      if (__popcll(__ballot(mine)) < 2) continue;  // (wave-uniform) the leader stands alone: its own atomic below
+      const u32 best = wave_max(mine ? rank : 0u);
+      if (lane == leader) atomicMax((unsigned long long *)(t.win + s), (unsigned long long)(batch | best));
+      todo = todo && !mine;
+    }
+    if (todo) atomicMax((unsigned long long *)(t.win + slot), (unsigned long long)(batch | rank));
+  }
+  // one atomic per wave per counter
+  n_new = wave_sum(n_new), n_drop = wave_sum(n_drop), n_seen = wave_sum(n_seen);
+  if (lane == 0) {
+    if (n_new) atomicAdd((unsigned long long *)(t.counters + 0), (unsigned long long)n_new);
+    if (n_drop) atomicAdd((unsigned long long *)(t.counters + 1), (unsigned long long)n_drop);
+    if (n_seen) atomicAdd((unsigned long long *)(t.counters + 3), (unsigned long long)n_seen);
+  }
+}
+
+struct AccArgs {
+  TableGeom t;
+  const uint8_t *records;
+  u64 record_stride;
+  u64 m;
+  const u32 *slots;        // INSERT: k_table_acc_claim's
+  const uint8_t *creator;  // INSERT
+  uint8_t *status;         // may be null
+  u64 value_offset;        // of the region inside a row (a multiple of sizeof(T))
+  u64 elems;               // elements of T in the region
+  u32 gshift;              // log2 of the lane group (G = the power of two >= elems, at most 64)
+};
+
+// T: u32, u64 (two's complement sums of either signedness) or double.  A group of G lanes per record,
+// lane l of it element l; 64 / G records per wave instruction.  COMBINE: the in-wave sums (the product's
+// form; the A/B alternative posts every addend on its own).
+template <class T, bool INSERT, bool COMBINE>
+__global__ __launch_bounds__(kBlock) void k_table_acc(const AccArgs a) {
+  typedef typename AccWord<T>::type W;
+  const TableGeom &t = a.t;
+  const u32 lane = threadIdx.x & 63;
+  const u64 wave = (u64)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  const u64 nwaves = (u64)gridDim.x * kWavesPerBlock;
+  if (INSERT && wave == 0 && lane == 0) t.counters[2] += 1;  // nothing in this kernel reads it
+  const u32 G = 1u << a.gshift, l = lane & (G - 1), g = lane >> a.gshift, rpi = 64u >> a.gshift;
+  for (u64 base = wave * rpi; base < a.m; base += nwaves * rpi) {  // (base is wave-uniform)
+    const u64 p = base + g;
+    const bool live = p < a.m;
+    u32 slot = kTableNoSlot;
+    if (live) {
+      if constexpr (INSERT)
+        slot = a.slots[p];
+      else
+        slot = table_find(t, *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16));
+    }
+    const bool has = slot != kTableNoSlot;
+    const T *add = reinterpret_cast<const T *>(a.records + (live ? p : 0) * a.record_stride + 24 + a.value_offset);
+    T *sum = reinterpret_cast<T *>(t.rows + (u64)(has ? slot : 0) * t.rowbytes + a.value_offset);
+    if (a.elems <= G) {  // (wave-uniform)
+      const bool on = has && l < a.elems;
+      const T v = on ? add[l] : acc_neutral<T>();
+      bool todo = on;
+      if (COMBINE && rpi > 1) {
+        bool cand = has;  // a group's lanes stand and fall together
+#pragma unroll
+        for (int k = 0; k < kLocateLeaders; ++k) {
+          const u64 open = __ballot(cand);
+          if (!open) break;  // (wave-uniform)
+          const u32 leader = (u32)__ffsll((unsigned long long)open) - 1;  // lane 0 of its group
+          const u32 s = (u32)__shfl((int)slot, (int)leader);
+          const bool mine = cand && slot == s;
+          cand = cand && !mine;
+          if ((u32)__popcll(__ballot(mine)) <= G) continue;  // (wave-uniform) one group: its own atomics below
+          T part = mine ? v : acc_neutral<T>();  // (v is neutral in the lanes past the region)
+          for (u32 o = 32; o >= G; o >>= 1) part += acc_shfl_xor(part, (int)o);  // over the groups, element by element
+          if (mine && g == (leader >> a.gshift) && l < a.elems) acc_add(sum + l, part);
+          todo = todo && !mine;
+        }
+      }
+      if (todo) acc_add(sum + l, v);
+    } else if (has) {  // more elements than a wave has lanes: G = 64, one record per wave
+      for (u64 c = l; c < a.elems; c += 64) acc_add(sum + c, add[c]);
+    }
+    if constexpr (INSERT) {
+      if (has && a.creator[p]) {  // (has implies live)
+        // the winner word of a slot this batch created carries this batch's number and its first position
+        const u64 f = 0xFFFFFFFFu - (u32)t.win[slot];
+        const W *src = reinterpret_cast<const W *>(a.records + f * a.record_stride + 24);
+        W *dst = reinterpret_cast<W *>(t.rows + (u64)slot * t.rowbytes);
+        const u64 lo = a.value_offset / sizeof(T), hi = lo + a.elems, n = t.rowbytes / sizeof(T);
+        for (u64 c = l; c < n; c += G)
+          if (c < lo || c >= hi) dst[c] = src[c];
+      }
+    }
+    if (a.status && l == 0 && live) a.status[p] = has ? 0 : INSERT ? 2 : 3;
+  }
+}
+
+}  // namespace pdht

@@ -42,5 +42,8 @@ static inline bool hook_table_reply_nt(bool dflt) { return tuning_variant() == 3
 static inline bool hook_table_put_nt(bool dflt) { return tuning_variant() == 341 ? !dflt : dflt; }
 // 342: the table export's outputs stored in the other policy
 static inline bool hook_table_export_nt(bool dflt) { return tuning_variant() == 342 ? !dflt : dflt; }
+// 344: the accumulate posts every addend with an atomic of its own (no in-wave sums); int32 / int64 only,
+// the launcher never asks for doubles (EXPERIMENTS.md §R12)
+static inline bool hook_table_acc_combine(bool dflt) { return tuning_variant() == 344 ? false : dflt; }
 
 }  // namespace pdht
