@@ -35,7 +35,8 @@
  * table from different streams are undefined.  No call here blocks, spins or
  * takes a lock; every probe is bounded by the capacity, so a full table ends
  * the call normally.  All can be captured into a graph.  A table takes 2^32
- * put, update and cswap batches between two pdht_table_init_dev calls.
+ * put, update, cswap, inserting-accumulate and add batches, of all kinds
+ * together, between two pdht_table_init_dev calls.
  */
 #ifndef PDHT_HIP_TABLE_H_
 #define PDHT_HIP_TABLE_H_
@@ -102,9 +103,11 @@ int pdht_table_get_dev(const void *table, uint64_t capacity, size_t rowbytes,
                        pdht_hip_stream_t stream);
 
 /* counts4[0..3] (device, 8-byte aligned) = entries stored / records dropped,
- * cumulative / batches that used the winner words (put, and the update and
- * cswap of pdht_hip_table_rmw.h) / slots inspected by puts, cumulative (a
- * retry on one slot after a lost compare-and-swap is not a new slot). */
+ * cumulative / batches that used the winner words (put, the update and
+ * cswap of pdht_hip_table_rmw.h, the inserting accumulate of
+ * pdht_hip_table_acc.h and the add of pdht_hip_table_add.h) / slots inspected
+ * by puts, inserting accumulates and adds, cumulative (a retry on one slot
+ * after a lost compare-and-swap is not a new slot). */
 int pdht_table_counts_dev(const void *table, uint64_t *counts4, pdht_hip_stream_t stream);
 
 /* ---- resolve (client side) ------------------------------------------------ */

@@ -34,9 +34,11 @@
  * from counts4[2], which they advance by one as a put does: counts4[2] of
  * pdht_table_counts_dev is "batches that used the winner words (put, update,
  * cswap)", and a table takes 2^32 such batches, of all three kinds together,
- * between two pdht_table_init_dev calls.  Calls on one stream are ordered by
- * the stream; concurrent calls on one table from different streams are
- * undefined.  Each call is two kernels with nothing but the kernel boundary
+ * between two pdht_table_init_dev calls -- together also with the inserting
+ * accumulate of pdht_hip_table_acc.h and the add of pdht_hip_table_add.h,
+ * which take their batch numbers from the same word.  Calls on one stream
+ * are ordered by the stream; concurrent calls on one table from different
+ * streams are undefined.  Each call is two kernels with nothing but the kernel boundary
  * between them: nothing blocks, spins or takes a lock, and both can be
  * captured into a graph.
  */

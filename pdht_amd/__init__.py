@@ -147,6 +147,8 @@ def _declare(L, tuning=False):
         "pdht_table_acc_workspace_bytes": (C.c_size_t, [_S, C.c_uint]),
         "pdht_table_acc_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, C.c_int, C.c_int, _S, _S, C.c_uint, _V, _S,
                                                  _V, _V]),
+        "pdht_table_add_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_add_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _V, _V, _S, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
@@ -903,6 +905,9 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   (include/pdht_hip_table_rmw.h: pdht_update, pdht_atomic_cswap)
 #   accumulate: bucket_put_records -> dist.exchange_records -> DeviceTable.acc_records
 #   (include/pdht_hip_table_acc.h: pdht_acc)
+#   create: bucket_put_records -> dist.exchange_records -> DeviceTable.add_records(replies=True)
+#        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
+#   (include/pdht_hip_table_add.h: the Portals put, the first record of an mbits wins)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -943,6 +948,14 @@ def table_acc_workspace_bytes(m: int, insert: bool = False) -> int:
     if not 0 <= m < (1 << 32):
         raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
     return lib().pdht_table_acc_workspace_bytes(m, PDHT_ACC_INSERT if insert else 0)
+
+
+def table_add_workspace_bytes(m: int) -> int:
+    """Bytes of workspace DeviceTable.add_records needs for m records: 4*m +
+    m rounded up to 4."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_add_workspace_bytes(m)
 
 
 def _acc_datatype(dtype):
@@ -1103,6 +1116,58 @@ class DeviceTable:
                    "pdht_table_acc_records_dev")
         return status
 
+    def add_records(self, records, status=True, replies=None, workspace=None, stream=None):
+        """Applies a batch of put records as the Portals put would one after
+        the other (libpdht/poll.c:205-263; pdht_table_add_records_dev): find
+        by mbits, insert the record's row if the entry is absent, do nothing
+        if it is there.  The first record of a new mbits wins, an entry that
+        is present keeps every byte.  records, status (True, a uint8 [m]
+        tensor, or False / None) and counts() as in put_records; status: 0
+        created by this record / 4 exists, from before or from an earlier
+        record of the batch / 2 dropped, table full.  replies: None / False =
+        none; True = a new uint8 [m, 8 + rowbytes]; a uint8 [m, 8 + rowbytes]
+        tensor or row-strided view (8-byte aligned, row stride a multiple of
+        8) = filled.  Reply p is the head-8 reply a get after the call would
+        give for record p's mbits (byte 0 = 0 and zeros for a dropped one),
+        for dist.exchange_replies and get_resolve.  Returns status without
+        replies, (status, replies) with them.  workspace: uint8, >=
+        table_add_workspace_bytes(m) bytes (allocated if None)."""
+        torch = _torch()
+        m, B, stride = _rows_2d(records, "records", self.device)
+        if B < 24 + self.rowbytes:
+            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
+        if stride % 8 or records.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        if status is True:
+            status = torch.empty(m, dtype=torch.uint8, device=self.device)
+        elif status is False or status is None:
+            status = None
+        else:
+            _need(status, "status", torch.uint8, self.device, shape=(m,))
+        rb, rstride = 8 + self.rowbytes, 0
+        if replies is True:
+            replies = torch.empty((m, rb // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, rb)
+        elif replies is False or replies is None:
+            replies = None
+        if replies is not None:
+            om, oB, rstride = _rows_2d(replies, "replies", self.device)
+            if (om, oB) != (m, rb):
+                raise ValueError(f"replies must have shape [{m}, {rb}], got {tuple(replies.shape)}")
+            if rstride % 8 or replies.data_ptr() % 8:
+                raise ValueError("replies must be 8-byte aligned with a row stride that is a multiple of 8")
+        need = lib().pdht_table_add_workspace_bytes(m)
+        if workspace is None:
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 4:
+                raise ValueError("workspace must be 4-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_add_records_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records),
+                                                    stride, m, _dptr(workspace), workspace.numel(), _opt(status),
+                                                    _opt(replies), rstride, g.stream), "pdht_table_add_records_dev")
+        return status if replies is None else (status, replies)
+
     def get(self, mbits_or_records, head: int = 8, out=None, stream=None):
         """Answers a batch of requests as init.c:192-220 does: replies uint8
         [m, head + rowbytes], byte 0 = 1 found / 0 not found, bytes 1..head-1
@@ -1198,8 +1263,9 @@ class DeviceTable:
         return out
 
     def counts(self):
-        """(entries stored, records dropped, batches applied -- put, update
-        and cswap --, slots inspected by puts); the last three cumulative.
+        """(entries stored, records dropped, batches applied -- put, update,
+        cswap, inserting accumulate and add --, slots inspected by puts,
+        inserting accumulates and adds); the last three cumulative.
         Host-synchronous."""
         return tuple(int(x) for x in self.counts_dev().cpu().tolist())
 
