@@ -36,7 +36,16 @@
  * takes a lock; every probe is bounded by the capacity, so a full table ends
  * the call normally.  All can be captured into a graph.  A table takes 2^32
  * put, update, cswap, inserting-accumulate and add batches, of all kinds
- * together, between two pdht_table_init_dev calls.
+ * together, between two pdht_table_init_dev calls.  The number taken so far
+ * is counts4[2] of pdht_table_counts_dev: a long-lived owner reads it and
+ * renews the numbers before it reaches 2^32 -- by a rehash into a new table
+ * (pdht_hip_table_iter.h: export as records, then one put; the new table
+ * starts from the few batches of that put), or by pdht_table_init_dev when
+ * the table may be emptied.  Nothing checks the limit: past it the batch
+ * number in the winner words wraps, older winner words beat newer ones, and
+ * puts are silently lost (status says "superseded" and the row is not
+ * written).  How many batches per second an owner applies is unmeasured, so
+ * no lifetime in hours is given here.
  */
 #ifndef PDHT_HIP_TABLE_H_
 #define PDHT_HIP_TABLE_H_

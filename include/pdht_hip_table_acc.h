@@ -51,9 +51,19 @@
  * order: with n addends x_1 .. x_n of one word, the word's old value among
  * them (+0.0 for an entry the call creates),
  *   |result - exact sum| <= gamma_n * sum |x_i|,
- *   gamma_n = n*u / (1 - n*u),  u = 2^-53.
+ *   gamma_n = n*u / (1 - n*u),  u = 2^-53,
+ * while no partial sum overflows (an order that passes DBL_MAX on the way
+ * leaves an infinity even where the exact sum is finite).
  * Sums whose every partial sum is an integer below 2^53 in magnitude are
- * exact and therefore reproducible.  The sign of a zero: adding into a present
+ * exact and therefore reproducible.  Special values follow IEEE 754 addition
+ * in whatever order the schedule picks, in the in-wave sums and in the atomics
+ * alike: a word with a NaN among its old value and addends ends NaN (the
+ * payload is not specified); +inf without -inf and NaN ends +inf, the
+ * mirrored case -inf, both together NaN; addends of one sign whose exact sum
+ * passes DBL_MAX end in that infinity.  Subnormals are not flushed, neither as
+ * addends nor as results: every double is a multiple of 2^-1074, and words
+ * whose sum |x_i| stays below 2^53 * 2^-1074 add exactly -- down to an exact
+ * +0.0 and up across 2^-1022 into the normals.  The sign of a zero: adding into a present
  * entry keeps it as some sequential order would (-0.0 + -0.0 = -0.0); an
  * entry the call creates starts from +0.0, so a created word whose records
  * all carry -0.0 holds +0.0 where the first record's own bytes are -0.0.  A

@@ -1078,8 +1078,14 @@ class DeviceTable:
         status: 0 added / 2 dropped / 3 not found (True, a uint8 [m] tensor,
         or False / None as in put_records).  Integers wrap and the result is
         byte-exact; float64 sums are added in an order the schedule picks
-        (within n*u/(1 - n*u) * sum|x_i| of the exact sum, u = 2^-53), and
-        the table must be in ordinary device memory.  workspace: uint8, >=
+        (within n*u/(1 - n*u) * sum|x_i| of the exact sum, u = 2^-53, while
+        no partial sum overflows).  NaN and infinities propagate as IEEE
+        addition has it in any order: a NaN among old value and addends gives
+        NaN, +inf alone +inf, -inf alone -inf, both NaN, and addends of one
+        sign whose exact sum passes DBL_MAX give that infinity.  Subnormals
+        are not flushed: multiples of 2^-1074 whose magnitudes sum to less
+        than 2^53 of them add exactly.  The table must be in ordinary device
+        memory.  workspace: uint8, >=
         table_acc_workspace_bytes(m, insert) bytes (allocated if None)."""
         torch = _torch()
         datatype, size = _acc_datatype(dtype)

@@ -465,3 +465,210 @@ def test_acc_on_a_side_stream_with_a_caller_workspace(dev):
         with pytest.raises(ValueError):
             tab.acc_records(rec, torch.int64, vo, insert=True, workspace=ws[:-4])
     assert (results[0] == results[1]).all()
+
+
+# ===================================================== IEEE specials ===
+# NaN, infinities, sums that overflow and subnormals in the double accumulate.  The position-order model cannot
+# say what these give (math.fsum raises on inf - inf and on overflow), so the expectation is computed here from
+# rules that hold in ANY order of the additions -- tests/test_table_ranges_cpu.py checks special_expect against
+# exact arithmetic on every input set below, in random sequential and tree orders.
+SPECIAL_RULES = ("nan", "pinf", "ninf", "both", "overflow", "sub", "sub_zero", "sub_cross")
+SPECIAL_REGIONS = ((24, 8, 2), (272, 8, 33), (48, 8, 5))  # (B, vo, elems): groups of 2 lanes; one record per
+#                                                            wave, pure atomics; 5 elements in a 48-B row at +8
+SPECIAL_SHAPES = ("m65", "one_mbits", "three_per_wave", "five_per_wave", "absent_mixed")
+DBL_OVER = 1 << 1024  # anything that rounds to here or beyond is +inf (the threshold is 2^1024 - 2^970)
+
+
+def _unit_exponent(x):
+    """e with x = odd * 2^e (x finite, non-zero)."""
+    num, den = abs(x).as_integer_ratio()
+    return (num & -num).bit_length() - 1 - (den.bit_length() - 1)
+
+
+def special_expect(xs):
+    """What a word holds after xs[0] + xs[1] + ... added in ANY order or tree (xs[0]: the old value, +0.0 for an
+    entry the call creates), or ValueError when no rule decides it:
+      a NaN among them -> NaN (the payload is not specified);
+      +inf and -inf -> NaN; only +inf -> +inf; only -inf -> -inf;
+      finite, all multiples of one power of two 2^e with sum|x_i| < 2^53 * 2^e: every partial sum is such a
+        multiple below 2^53 of them, so no addition rounds and the result is the exact sum (integers below
+        2^53, multiples of 2^-1074 whether subnormal or just normal, a single non-zero value); a zero result is
+        +0.0 (no -0.0 may be among the xs: a zero sum then comes from a cancellation or from +0.0 + +0.0);
+      finite and all of one sign with |exact sum| * (1 - gamma_n) >= 2^1024: had no partial sum overflowed, the
+        result would be within gamma_n of the exact sum and so past DBL_MAX; one did, and sums of one sign never
+        come back from an infinity."""
+    import math
+    from fractions import Fraction
+    xs = [float(x) for x in xs]
+    if any(math.isnan(x) for x in xs):
+        return math.nan
+    pos, neg = math.inf in xs, -math.inf in xs
+    if pos or neg:
+        return math.nan if pos and neg else math.inf if pos else -math.inf
+    if any(x == 0 and math.copysign(1.0, x) < 0 for x in xs):
+        raise ValueError("-0.0 among the addends: the sign of a zero sum depends on the order")
+    nz = [x for x in xs if x != 0]
+    if not nz:
+        return 0.0
+    e = min(_unit_exponent(x) for x in nz)
+    exact = sum(Fraction(x) for x in nz)
+    total = sum(abs(Fraction(x)) for x in nz)
+    if total < Fraction(2) ** (53 + e) and total < DBL_OVER:
+        return float(exact)  # representable: an integer below 2^53 times 2^e, e >= -1074, below 2^1024
+    n = len(xs)
+    one_sign = all(x > 0 for x in nz) or all(x < 0 for x in nz)
+    if one_sign and abs(exact) * (1 - Fraction(n, (1 << 53) - n)) >= DBL_OVER:
+        return math.inf if exact > 0 else -math.inf
+    raise ValueError("no order-independent rule for these addends")
+
+
+def special_word(rule, r, has_old, rng, ki):
+    """(old value or None, r addends) of one word under `rule`; "ordinary": integer-valued, |x| < 2^20."""
+    import math
+    add = [float(x) for x in rng.integers(-(1 << 20), 1 << 20, r)]
+    old = float(rng.integers(-(1 << 20), 1 << 20)) if has_old else None
+    if rule in ("nan", "pinf", "ninf"):
+        v = {"nan": math.nan, "pinf": math.inf, "ninf": -math.inf}[rule]
+        if has_old and ki % 3 == 2:
+            old = v  # the entry holds it, the records are ordinary
+        else:
+            add[int(rng.integers(0, r)) if has_old else 0] = v  # a created entry: its first record carries it
+    elif rule == "both":
+        if has_old:
+            old, add[int(rng.integers(0, r))] = math.inf, -math.inf
+        else:
+            add[0] = math.inf
+            if r >= 2:
+                add[r - 1] = -math.inf
+    elif rule == "overflow":
+        add = [1e308] * r
+        old = 1e308 if has_old else None
+    elif rule in ("sub", "sub_zero", "sub_cross"):
+        if rule == "sub_cross":  # the sum ends at or above 2^52 units = 2^-1022, the smallest normal
+            k = [(1 << 52) // r + int(x) for x in rng.integers(-1000, 1000, r)]
+            k0 = 2000 * r + 7
+            if not has_old:
+                k[r - 1] += k0
+            assert sum(k) + (k0 if has_old else 0) >= 1 << 52
+        else:
+            k = [int(x) * int(s) for x, s in zip(rng.integers(1, 1 << 20, r), rng.choice([-1, 1], r))]
+            k0 = int(rng.integers(1, 1 << 20))
+            if rule == "sub_zero":  # ends exactly 0 after being non-zero
+                if has_old:
+                    if sum(k) == 0:
+                        k[0] += 1
+                    k0 = -sum(k)
+                elif r >= 2:
+                    if sum(k[:-1]) == 0:
+                        k[0] += 1
+                    k[r - 1] = -sum(k[:-1])
+        add = [math.ldexp(x, -1074) for x in k]
+        old = math.ldexp(k0, -1074) if has_old else None
+    else:
+        assert rule == "ordinary"
+    return old, add
+
+
+def special_batch(rule, shape, elems, insert, seed=0):
+    """The inputs of one special-values batch, made without a GPU: (held, old [n, elems], absent, mb, add [m,
+    elems], rule_of) -- a table of the 80 mbits `held` (mbits 0 among them) whose words hold `old`, a batch of
+    the shape `shape` of batch_shapes over them, and the rule of every word (mbits, element) the batch adds
+    into: `rule` where (index of the mbits by first appearance + element) is even, "ordinary" elsewhere.
+    insert: the batch goes to an EMPTY table with insert=True, so every word starts from +0.0."""
+    held = np.concatenate([np.zeros(1, np.uint64), distinct_mbits(79, 2950)])
+    absent = distinct_mbits(10, 2951)
+    mb = batch_shapes(held, absent)[shape]
+    rng = np.random.default_rng(2952 + seed + 7 * SPECIAL_RULES.index(rule) + 101 * SPECIAL_SHAPES.index(shape) + elems)
+    old = rng.integers(-(1 << 20), 1 << 20, (len(held), elems)).astype(np.float64)
+    add = np.zeros((len(mb), elems))
+    row_of = {int(k): i for i, k in enumerate(held)}
+    rule_of = {}
+    order = []
+    for k in mb.tolist():
+        if k not in order:
+            order.append(k)
+    for ki, k in enumerate(order):
+        at = np.flatnonzero(mb == np.uint64(k))
+        present = not insert and k in row_of
+        for j in range(elems):
+            what = rule if (ki + j) % 2 == 0 else "ordinary"
+            o, a = special_word(what, len(at), present, rng, ki)
+            add[at, j] = a
+            if present:
+                old[row_of[k], j] = o
+            if present or insert:
+                rule_of[(k, j)] = what
+    return held, old, absent, mb, add, rule_of
+
+
+def special_words(held, old, mb, add, insert):
+    """{(mbits, element): [old value or +0.0, the addends in position order]} of every word the batch adds into."""
+    row_of = {} if insert else {int(k): i for i, k in enumerate(held)}
+    words = {}
+    for p, k in enumerate(mb.tolist()):
+        if not insert and k not in row_of:
+            continue
+        for j in range(add.shape[1]):
+            words.setdefault((k, j), [0.0 if insert else float(old[row_of[k], j])]).append(float(add[p, j]))
+    return words
+
+
+@pytest.mark.parametrize("B,vo,elems", SPECIAL_REGIONS)
+@pytest.mark.parametrize("rule", SPECIAL_RULES)
+def test_special_doubles_follow_ieee_in_any_order(dev, rule, B, vo, elems):
+    """NaN, +-inf, inf - inf, sums that overflow and subnormals (exact multiples of 2^-1074: sums that end 0, and
+    sums that cross into the normals at 2^-1022), in every other word of a batch; the words between them take
+    integer-valued addends.  Distinct mbits (one atomic per record), one hot mbits and three and five mbits per
+    wave (in-wave sums, then one atomic), mixed with absent ones; 33 elements (one record per wave, pure
+    atomics, no in-wave sum) and 5 elements in a 48-B row at +8; present entries, and insert=True on an empty
+    table, where the first record carries the special value and the word starts from +0.0.  Each word against
+    special_expect (NaN by isnan, everything else bit for bit); the ordinary words also against the
+    position-order sum; every byte outside the region, the status and the counters against the model."""
+    import math
+    region = np.s_[8 + vo:8 + vo + 8 * elems]
+    for shape in SPECIAL_SHAPES:
+        for insert in (False, True):
+            held, old, absent, mb, add, rule_of = special_batch(rule, shape, elems, insert)
+            m = len(mb)
+            rows = rows_with(m, B, vo, add, 2960)
+            if insert:
+                tab, state = P.DeviceTable(256, B, dev), {}
+                first = {int(k): rows[i] for i, k in reversed(list(enumerate(mb)))}
+                state = {k: r.copy() for k, r in first.items()}  # outside the region: the FIRST record's bytes
+                want_st = np.zeros(m, np.uint8)
+            else:
+                tab, state = filled(dev, 256, B, held, rows_with(len(held), B, vo, old, 2961))
+                want_st = np.where(np.isin(mb, held), 0, 3).astype(np.uint8)
+            before = tab.counts()
+            st = tab.acc_records(rec_to_dev(forge(mb, rows, 24 + B), dev), torch.float64, vo, elems, insert=insert)
+            assert P.last_kernel() == ("k_table_acc_claim+k_table_acc<f64,insert>" if insert else "k_table_acc<f64>")
+            assert (st.cpu().numpy() == want_st).all()
+            after = tab.counts()
+            if insert:
+                assert after[:3] == (len(state), 0, 1) and after[3] >= m
+            else:
+                assert after == before
+            q = np.concatenate([held, absent])
+            got = tab.get(i64(q, dev)).cpu().numpy()
+            want = replies8(state, q, B)
+            assert (np.delete(got, region, axis=1) == np.delete(want, region, axis=1)).all()
+            gotw = np.ascontiguousarray(got[:, region]).view(np.float64)
+            words = special_words(held, old, mb, add, insert)
+            assert set(words) == set(rule_of) and rule in rule_of.values() and "ordinary" in rule_of.values()
+            at = {int(k): i for i, k in enumerate(q)}
+            for i, k in enumerate(q.tolist()):  # the words no record named keep what they held
+                for j in range(elems):
+                    if (k, j) not in words and k in state:
+                        assert gotw[i, j].tobytes() == np.float64(old[i, j]).tobytes()
+            bad = []
+            for (k, j), xs in words.items():
+                g, w = float(gotw[at[k], j]), special_expect(xs)
+                if rule_of[(k, j)] == "ordinary":
+                    seq = np.float64(xs[0])
+                    for x in xs[1:]:
+                        seq = seq + np.float64(x)
+                    assert float(seq) == w and not math.isnan(w)  # the integer-valued-doubles rule
+                same = math.isnan(g) if math.isnan(w) else np.float64(g).tobytes() == np.float64(w).tobytes()
+                if not same:
+                    bad.append((shape, insert, rule_of[(k, j)], len(xs) - 1, g.hex(), w.hex()))
+            assert not bad, bad[:8]

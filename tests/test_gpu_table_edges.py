@@ -461,3 +461,173 @@ def test_caller_owned_storage(dev, B):
     zrow = orows[np.flatnonzero(over == 0)[-1]]
     assert zero[0] == 1 and (zero[8:] == zrow).all()
     assert (buf[off + nbytes - B:off + nbytes].cpu().numpy() == zrow).all()  # slot C: the last thing written
+
+
+# ------------------------------------------------------- 8. high batch numbers ---
+# "A table takes 2^32 batches between two inits" (include/pdht_hip_table.h): the winner word is
+# (counters[2] << 32) | position under an unsigned 64-bit atomicMax, in five claim / locate kernels and four second
+# kernels.  counters[2] is the u64 at byte 16 of the table's buffer (tests/table_iter_ref.py has the layout); a
+# test may move it FORWARD, which leaves the older winner words with smaller numbers -- the state of a long-lived
+# table.
+import table_acc_ref as ACCR  # noqa: E402
+import table_add_ref as ADDR  # noqa: E402
+import table_rmw_ref as RMWR  # noqa: E402
+from test_gpu_table_add import check_table, rec_at, replies8, run_add  # noqa: E402
+
+EVERY_KIND = ["add", "put", "update", "cswap", "acc", "add", "put", "add", "cswap",
+              "add", "update", "add", "acc", "cswap", "add", "put", "add"]  # seventeen batches, no clear
+
+
+def set_batch_number(tab, v):
+    assert tab.counts()[2] <= v < 1 << 32  # forward only, inside the contract
+    tab.storage[16:24].view(torch.int64).fill_(v)
+    assert tab.counts()[2] == v
+
+
+def one_batch(tab, state, what, mb, rows, dev):
+    """One batch of the kind `what` on the device and on the dict model: status / replies compared."""
+    B, m = tab.rowbytes, len(mb)
+    rec = rec_at(forge(mb, rows, 24 + B), dev)
+    if what == "add":
+        run_add(tab, state, mb, rows, dev)
+    elif what == "put":
+        st = tab.put_records(rec).cpu().numpy()
+        last = m - 1 - np.unique(mb[::-1], return_index=True)[1]
+        want = np.ones(m, np.uint8)
+        want[last] = 0
+        assert (st == want).all()
+        for p in last:
+            state[int(mb[p])] = rows[p].copy()
+    elif what == "update":
+        assert (tab.update_records(rec).cpu().numpy() == RMWR.update_ref(state, mb, rows)).all()
+    elif what == "cswap":
+        held = [k for k in mb.tolist() if k in state]
+        word = int(state[held[0]][8:16].view(np.uint64)[0])  # what one of the entries holds: it swaps
+        got = tab.cswap(rec, 8, word, 77).cpu().numpy()
+        assert (got == RMWR.cswap_ref(state, mb, 8, word, 77)).all()
+    else:
+        assert what == "acc"
+        st = tab.acc_records(rec, torch.int64, 16, insert=True).cpu().numpy()
+        assert (st == ACCR.acc_ref(state, mb, rows, np.int64, 16, 1, True, capacity=tab.capacity)[0]).all()
+
+
+@pytest.mark.parametrize("start", [(1 << 31) - 9, (1 << 32) - 17], ids=["across_bit_31", "up_to_2_32"])
+def test_seventeen_batches_of_every_kind_at_high_batch_numbers(dev, start):
+    """A 256-slot table that took one batch of every kind at small numbers, then counters[2] moved to 2^31 - 9
+    (bit 31 of the batch number is set from the tenth batch on) or to 2^32 - 17 (the last batch carries number
+    2^32 - 1 and leaves counts()[2] == 2^32, where the contract ends): add / put / update / cswap / inserting
+    accumulate in turn over one pool of mbits with heavy repeats and mbits 0.  After every batch the status, the
+    replies, the three counters and the whole table (get and export) against the dict models."""
+    B, C = 24, 256
+    pool = np.concatenate([np.zeros(1, np.uint64), distinct_mbits(130, 8300)])
+    rng = np.random.default_rng(8301)
+    tab, state, batches = P.DeviceTable(C, B, dev), {}, 0
+    for t, what in enumerate(["add", "put", "update", "cswap", "acc"]):
+        mb = pool[rng.integers(0, 40, 300)]
+        one_batch(tab, state, what, mb, rows_for(300, B, 8302 + t), dev)
+        batches += 1
+        assert tab.counts()[:3] == (len(state), 0, batches)
+    set_batch_number(tab, start)
+    batches = start
+    for t, what in enumerate(EVERY_KIND):
+        m = int(rng.integers(300, 600))
+        mb = pool[rng.integers(0, 60 + 4 * t, m)]
+        mb[rng.integers(0, m, 3)] = 0
+        assert (mb == 0).any() and len(np.unique(mb)) < m // 2  # mbits 0, heavy repeats
+        one_batch(tab, state, what, mb, rows_for(m, B, 8310 + t), dev)
+        batches += 1
+        entries, dropped, nb = tab.counts()[:3]
+        assert (entries, dropped) == (len(state), 0) and isinstance(nb, int) and nb == batches
+        check_table(tab, state, pool, dev)
+    assert len(EVERY_KIND) == 17 and batches == start + 17
+    assert (start < 1 << 31 < batches) or batches == 1 << 32
+
+
+def test_put_cswap_add_in_a_graph_across_bit_31(dev):
+    """One captured graph of put(a) -> cswap -> add(c), captured with counters[2] at 2^31 - 2 and replayed three
+    times: the nine batches carry the numbers 2^31 - 2 .. 2^31 + 6, and the model is stepped along."""
+    B, m, C = 40, 900, 1024
+    keys = distinct_mbits(400, 8400)
+    rng = np.random.default_rng(8401)
+    batch = {x: keys[rng.integers(lo, hi, m)] for x, (lo, hi) in dict(a=(0, 250), b=(100, 300), c=(150, 400)).items()}
+    rows = {x: rows_for(m, B, 8402 + i) for i, x in enumerate("abc")}
+    rec = {x: rec_at(forge(batch[x], rows[x], 24 + B), dev) for x in "abc"}
+    both = next(k for k in batch["b"].tolist() if k in set(batch["a"].tolist()))
+    last_a = int(np.flatnonzero(batch["a"] == np.uint64(both)).max())  # the record of a whose row stays, and b asks
+    compare = int(rows["a"][last_a][8:16].view(np.uint64)[0])           # for its mbits: the cswap swaps on every replay
+    tab, state = P.DeviceTable(C, B, dev), {}
+    ws = torch.empty(P.table_add_workspace_bytes(m), dtype=torch.uint8, device=dev)
+    st = {x: torch.empty(m, dtype=torch.uint8, device=dev) for x in "ac"}
+    swapped = torch.empty((m, 16), dtype=torch.uint8, device=dev)
+    rep = torch.empty((m, 8 + B), dtype=torch.uint8, device=dev)
+
+    def step():
+        tab.put_records(rec["a"], status=st["a"], workspace=ws[:4 * m])
+        tab.cswap(rec["b"], 8, compare, 0x5555, out=swapped, workspace=ws[:4 * m])
+        tab.add_records(rec["c"], status=st["c"], replies=rep, workspace=ws)
+
+    def model_step():
+        want = {}
+        last = m - 1 - np.unique(batch["a"][::-1], return_index=True)[1]
+        want["a"] = np.ones(m, np.uint8)
+        want["a"][last] = 0
+        for p in last:
+            state[int(batch["a"][p])] = rows["a"][p].copy()
+        want["b"] = RMWR.cswap_ref(state, batch["b"], 8, compare, 0x5555)
+        assert (want["b"][:, 8:16] == np.frombuffer(np.uint64(compare).tobytes(), np.uint8)).all(1).any()
+        want["c"] = ADDR.add_ref(state, batch["c"], rows["c"], capacity=C)
+        return want
+
+    def compare_all(want):
+        assert (st["a"].cpu().numpy() == want["a"]).all() and (swapped.cpu().numpy() == want["b"]).all()
+        assert (st["c"].cpu().numpy() == want["c"][0]).all() and (rep.cpu().numpy() == want["c"][1]).all()
+        check_table(tab, state, keys, dev)
+
+    step()  # eager, at small numbers
+    compare_all(model_step())
+    first = (1 << 31) - 2
+    set_batch_number(tab, first)
+    torch.cuda.synchronize(dev)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        step()
+    assert tab.counts()[2] == first  # capture runs nothing
+    for k in (1, 2, 3):
+        for t in list(st.values()) + [swapped, rep]:
+            t.fill_(9)
+        g.replay()
+        torch.cuda.synchronize(dev)
+        compare_all(model_step())
+        assert tab.counts()[:3] == (len(state), 0, first + 3 * k)
+    assert first + 9 > 1 << 31
+
+
+def test_rehash_renews_the_batch_numbers(dev):
+    """With counters[2] at 2^32 - 1 the table can take one more batch; rehash (same capacity, and twice it) gives
+    tables with the same entries whose counts()[2] is the number of chunks that held an entry, and which take a
+    put / update / cswap batch with repeats as any young table does.  The old table is left untouched."""
+    B, C = 24, 256
+    pool = np.concatenate([np.zeros(1, np.uint64), distinct_mbits(170, 8500)])
+    rng = np.random.default_rng(8501)
+    tab, state = P.DeviceTable(C, B, dev), {}
+    for t, what in enumerate(["add", "put", "acc"]):
+        one_batch(tab, state, what, pool[rng.integers(0, 150, 500)], rows_for(500, B, 8502 + t), dev)
+    set_batch_number(tab, (1 << 32) - 1)
+    old_counts = tab.counts()
+    slots = tab.entries()[2].cpu().numpy().view(np.uint32).astype(np.int64)
+    assert len(slots) == len(state) > 100
+    S = 24 + B
+    for capacity, chunk_slots in ((C, None), (2 * C, 64), (C, 1)):
+        kw = {} if chunk_slots is None else dict(chunk_bytes=chunk_slots * S)
+        new = tab.rehash(capacity, **kw)
+        chunks = 1 if chunk_slots is None else len(np.unique(slots // chunk_slots))
+        assert new.counts()[:3] == (len(state), 0, chunks) and new.capacity == capacity
+        model = {k: v.copy() for k, v in state.items()}
+        check_table(new, model, pool, dev)
+        for t, what in enumerate(["put", "update", "cswap"]):
+            mb = pool[rng.integers(0, 171, 400)]
+            one_batch(new, model, what, mb, rows_for(400, B, 8510 + t), dev)
+            assert new.counts()[:3] == (len(model), 0, chunks + t + 1)
+            check_table(new, model, pool, dev)
+    assert tab.counts() == old_counts
+    check_table(tab, state, pool, dev)
