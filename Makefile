@@ -31,15 +31,15 @@ CFLAGS_SHIM = -std=c99 -O3 -fPIC -fvisibility=hidden -Wall -Wextra -Iinclude
 HIP_HDR := pdht_amd/csrc/city_core.h pdht_amd/csrc/kernels.h pdht_amd/csrc/runtime.h \
            pdht_amd/csrc/bucket.h pdht_amd/csrc/launch.h include/pdht_hip.h include/pdht_hip_put.h \
            include/pdht_hip_table.h include/pdht_hip_table_iter.h include/pdht_hip_table_rmw.h include/pdht_hip_table_acc.h \
-           include/pdht_hip_table_add.h include/pdht_hip_plan.h include/pdht_city.h
+           include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_plan.h include/pdht_city.h
 HDR_PRODUCT := $(wildcard pdht_amd/csrc/product/*.h)
 HDR_TUNING := $(wildcard pdht_amd/csrc/tuning/*.h) pdht_amd/csrc/pdht_hip_tuning.h
 SHIM_HDR := include/pdht_hash.h include/pdht_hip.h include/pdht_hip_put.h include/pdht_hip_table.h \
             include/pdht_hip_table_iter.h include/pdht_hip_table_rmw.h include/pdht_hip_table_acc.h \
-            include/pdht_hip_table_add.h include/pdht_hip_plan.h include/pdht_city.h
+            include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_plan.h include/pdht_city.h
 # the C-ABI in translation units that build in parallel (make -j)
 HIP_UNITS := pdht_hip pdht_fixed64 pdht_fixed128 pdht_var pdht_host pdht_bucket pdht_rows pdht_table pdht_table_iter \
-             pdht_table_rmw pdht_table_acc pdht_table_add
+             pdht_table_rmw pdht_table_acc pdht_table_add pdht_table_reduce
 OBJ_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.o) $(LIBDIR)/city_host.o
 OBJ_TUN_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.tun.o) $(LIBDIR)/city_host.o $(LIBDIR)/pdht_tuning.tun.o
 OBJ     := $(OBJ_ENG) $(LIBDIR)/pdht_hash.o
@@ -71,6 +71,9 @@ $(LIBDIR)/pdht_table_rmw.o $(LIBDIR)/pdht_table_rmw.tun.o: pdht_amd/csrc/table.h
 $(LIBDIR)/pdht_table_acc.o $(LIBDIR)/pdht_table_acc.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
     pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h pdht_amd/csrc/rows.h
 $(LIBDIR)/pdht_table_add.o $(LIBDIR)/pdht_table_add.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
+    pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_add.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h \
+    pdht_amd/csrc/rows.h
+$(LIBDIR)/pdht_table_reduce.o $(LIBDIR)/pdht_table_reduce.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
     pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_add.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h \
     pdht_amd/csrc/rows.h
 $(foreach u,pdht_fixed64 pdht_fixed128 pdht_var pdht_host,$(LIBDIR)/$(u).o $(LIBDIR)/$(u).tun.o): pdht_amd/csrc/launch.h

@@ -238,6 +238,8 @@ int pdht_hip_key_stream_var_dev(const void *bytes, size_t nbytes, const uint64_t
 #include "pdht_hip_table_acc.h"
 /* Insert-if-absent (the Portals put: the first record wins) on the table. */
 #include "pdht_hip_table_add.h"
+/* Reductions on the table's entries: min, max, and, or, xor beside the sum, with replies. */
+#include "pdht_hip_table_reduce.h"
 /* The 64-B kernel's launch plan and tile order (host arithmetic). */
 #include "pdht_hip_plan.h"
 

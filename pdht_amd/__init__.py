@@ -36,7 +36,7 @@ __all__ = [
     "device_count", "PdhtTable", "K2", "bucket_batch", "bucket_records", "record_fields",
     "bucket_record_bytes", "bucket_workspace_bytes", "WeakHashLen32WithSeeds", "WeakHashLen32WithSeeds6",
     "tuning", "last_kernel", "mpi_lib", "table_bytes", "table_reply_bytes", "DeviceTable", "get_resolve",
-    "table_export_workspace_bytes",
+    "table_export_workspace_bytes", "table_reduce_workspace_bytes",
 ]
 
 K2 = 0x9AE16A3B2F90404F  # city.c:96 (CityHash64WithSeed's seed0)
@@ -149,6 +149,9 @@ def _declare(L, tuning=False):
                                                  _V, _V]),
         "pdht_table_add_workspace_bytes": (C.c_size_t, [_S]),
         "pdht_table_add_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _V, _V, _S, _V]),
+        "pdht_table_reduce_workspace_bytes": (C.c_size_t, [_S, C.c_uint, C.c_int]),
+        "pdht_table_reduce_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, C.c_int, C.c_int, _S, _S, C.c_uint, _V,
+                                                    _S, _V, _V, _S, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
@@ -908,6 +911,9 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   create: bucket_put_records -> dist.exchange_records -> DeviceTable.add_records(replies=True)
 #        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
 #   (include/pdht_hip_table_add.h: the Portals put, the first record of an mbits wins)
+#   reduce: bucket_put_records -> dist.exchange_records -> DeviceTable.reduce_records(op, replies=True)
+#        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
+#   (include/pdht_hip_table_reduce.h: min, max, and, or, xor beside the sum)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -956,6 +962,35 @@ def table_add_workspace_bytes(m: int) -> int:
     if not 0 <= m < (1 << 32):
         raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
     return lib().pdht_table_add_workspace_bytes(m)
+
+
+# the reduce's operations (include/pdht_hip_table_reduce.h)
+PDHT_RED_ADD, PDHT_RED_MIN, PDHT_RED_MAX, PDHT_RED_AND, PDHT_RED_OR, PDHT_RED_XOR = 0, 1, 2, 3, 4, 5
+_RED_OPS = {"add": PDHT_RED_ADD, "min": PDHT_RED_MIN, "max": PDHT_RED_MAX, "and": PDHT_RED_AND, "or": PDHT_RED_OR,
+            "xor": PDHT_RED_XOR}
+
+
+def table_reduce_workspace_bytes(m: int, insert: bool = False, replies: bool = False) -> int:
+    """Bytes of workspace DeviceTable.reduce_records needs for m records: 0
+    without insert and replies, 4*m with replies only, 4*m + m rounded up to
+    4 with insert."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_reduce_workspace_bytes(m, PDHT_ACC_INSERT if insert else 0, 1 if replies else 0)
+
+
+def _red_op(op, dtype):
+    """op: a PDHT_RED_* int or its name -> the int; the bitwise ones are not
+    defined for float64."""
+    if isinstance(op, str):
+        if op not in _RED_OPS:
+            raise ValueError(f"op must be one of {sorted(_RED_OPS)} or a PDHT_RED_* constant, got {op!r}")
+        op = _RED_OPS[op]
+    if not isinstance(op, int) or isinstance(op, bool) or not PDHT_RED_ADD <= op <= PDHT_RED_XOR:
+        raise ValueError(f"op must be one of {sorted(_RED_OPS)} or a PDHT_RED_* constant, got {op!r}")
+    if op >= PDHT_RED_AND and dtype == _torch().float64:
+        raise ValueError("op and / or / xor is defined for torch.int32 and torch.int64 only")
+    return op
 
 
 def _acc_datatype(dtype):
@@ -1121,6 +1156,78 @@ class DeviceTable:
                                                     _dptr(workspace), workspace.numel(), _opt(status), g.stream),
                    "pdht_table_acc_records_dev")
         return status
+
+    def reduce_records(self, records, dtype, op, value_offset: int, elems: int = 1, insert: bool = False,
+                       status=True, replies=None, workspace=None, stream=None):
+        """acc_records with an operation of the caller's choice, and with
+        replies (pdht_table_reduce_records_dev): find by mbits and set the
+        `elems` elements of `dtype` at `value_offset` of the entry's row to
+        op(entry's, record's); no other byte of a present entry changes.
+        op: a PDHT_RED_* constant or "add", "min", "max", "and", "or", "xor".
+        add is acc_records' sum.  min and max compare torch.int32 /
+        torch.int64 as signed integers and torch.float64 by IEEE 754
+        totalOrder on the 64 bits (-NaN < -inf < .. < -0.0 < +0.0 < .. < +inf
+        < +NaN): the result is one operand's bits, NaNs and subnormals
+        included.  and, or, xor are bitwise, for the integer types only.
+        Every op but add on float64 is byte-exact against the records applied
+        one after the other, and the same on every run.  dtype, value_offset,
+        elems, insert, status (0 applied / 2 dropped / 3 not found) and
+        counts() as in acc_records.  replies as in add_records: None / False
+        = none; True = a new uint8 [m, 8 + rowbytes]; a uint8 [m, 8 +
+        rowbytes] tensor or row-strided view (8-byte aligned, row stride a
+        multiple of 8) = filled.  Reply p is the head-8 reply a get after the
+        call would give for record p's mbits -- the reduced entry, or byte 0
+        = 0 and zeros for a record with status 2 or 3.  Returns status
+        without replies, (status, replies) with them.  workspace: uint8, >=
+        table_reduce_workspace_bytes(m, insert, replies) bytes (allocated if
+        None)."""
+        torch = _torch()
+        datatype, size = _acc_datatype(dtype)
+        op = _red_op(op, dtype)
+        for name, v in (("value_offset", value_offset), ("elems", elems)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+        if value_offset % size or elems < 1 or value_offset + elems * size > self.rowbytes:
+            raise ValueError(f"the region must be elems >= 1 elements of {size} bytes at a value_offset that is a "
+                             f"multiple of {size}, inside the {self.rowbytes}-byte row; got value_offset "
+                             f"{value_offset}, elems {elems}")
+        m, B, stride = _rows_2d(records, "records", self.device)
+        if B < 24 + self.rowbytes:
+            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
+        if stride % 8 or records.data_ptr() % 8:
+            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        if status is True:
+            status = torch.empty(m, dtype=torch.uint8, device=self.device)
+        elif status is False or status is None:
+            status = None
+        else:
+            _need(status, "status", torch.uint8, self.device, shape=(m,))
+        rb, rstride = 8 + self.rowbytes, 0
+        if replies is True:
+            replies = torch.empty((m, rb // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, rb)
+        elif replies is False or replies is None:
+            replies = None
+        if replies is not None:
+            om, oB, rstride = _rows_2d(replies, "replies", self.device)
+            if (om, oB) != (m, rb):
+                raise ValueError(f"replies must have shape [{m}, {rb}], got {tuple(replies.shape)}")
+            if rstride % 8 or replies.data_ptr() % 8:
+                raise ValueError("replies must be 8-byte aligned with a row stride that is a multiple of 8")
+        flags = PDHT_ACC_INSERT if insert else 0
+        need = lib().pdht_table_reduce_workspace_bytes(m, flags, 1 if replies is not None else 0)
+        if workspace is None:
+            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        else:
+            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+            if workspace.data_ptr() % 4:
+                raise ValueError("workspace must be 4-byte aligned")
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_reduce_records_dev(_dptr(self.storage), self.capacity, self.rowbytes,
+                                                       _dptr(records), stride, m, datatype, op, value_offset, elems,
+                                                       flags, _dptr(workspace), workspace.numel(), _opt(status),
+                                                       _opt(replies), rstride, g.stream),
+                   "pdht_table_reduce_records_dev")
+        return status if replies is None else (status, replies)
 
     def add_records(self, records, status=True, replies=None, workspace=None, stream=None):
         """Applies a batch of put records as the Portals put would one after

@@ -120,9 +120,10 @@ extern "C" {
  *                     (product: plain)
  *                343  export: the write pass reads the ballot masks the count pass saved
  *                     in the workspace (1 bit per slot) instead of the tags again
- *                344  accumulate, int32 / int64: every addend posted with an atomic of its own
- *                     (product: lanes of a wave that share a slot add up first); doubles keep
- *                     the product's form under this variant, that kernel is not built
+ *                344  accumulate and reduce (every op), int32 / int64: every operand posted with an
+ *                     atomic of its own (product: lanes of a wave that share a slot combine first);
+ *                     doubles keep the product's form under this variant for every op, that kernel
+ *                     is not built
  *   host          61  chunked copy pipeline instead of zero-copy on pinned buffers
  *   small keys   219  8-B placement with a histogram, 4 keys per lane (the shape
  *                     before late r04; product: 8); 220 16 keys per lane
