@@ -39,7 +39,7 @@ SHIM_HDR := include/pdht_hash.h include/pdht_hip.h include/pdht_hip_put.h includ
             include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_plan.h include/pdht_city.h
 # the C-ABI in translation units that build in parallel (make -j)
 HIP_UNITS := pdht_hip pdht_fixed64 pdht_fixed128 pdht_var pdht_host pdht_bucket pdht_rows pdht_table pdht_table_iter \
-             pdht_table_rmw pdht_table_acc pdht_table_add pdht_table_reduce
+             pdht_table_rmw pdht_table_add pdht_table_reduce
 OBJ_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.o) $(LIBDIR)/city_host.o
 OBJ_TUN_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.tun.o) $(LIBDIR)/city_host.o $(LIBDIR)/pdht_tuning.tun.o
 OBJ     := $(OBJ_ENG) $(LIBDIR)/pdht_hash.o
@@ -62,20 +62,12 @@ product: $(LIB) $(LIB_MPI) $(LIB_TUN)
 # unit-specific headers
 $(LIBDIR)/pdht_bucket.o $(LIBDIR)/pdht_bucket.tun.o: pdht_amd/csrc/bucket.h pdht_amd/csrc/rows.h
 $(LIBDIR)/pdht_rows.o $(LIBDIR)/pdht_rows.tun.o: pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table.o $(LIBDIR)/pdht_table.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_geom.h \
-    pdht_amd/csrc/table_host.h pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table_iter.o $(LIBDIR)/pdht_table_iter.tun.o: pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h \
-    pdht_amd/csrc/table_iter.h pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table_rmw.o $(LIBDIR)/pdht_table_rmw.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
-    pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table_acc.o $(LIBDIR)/pdht_table_acc.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
-    pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table_add.o $(LIBDIR)/pdht_table_add.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
-    pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_add.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h \
-    pdht_amd/csrc/rows.h
-$(LIBDIR)/pdht_table_reduce.o $(LIBDIR)/pdht_table_reduce.tun.o: pdht_amd/csrc/table.h pdht_amd/csrc/table_rmw.h \
-    pdht_amd/csrc/table_acc.h pdht_amd/csrc/table_add.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h \
-    pdht_amd/csrc/rows.h
+TABLE_HDR := pdht_amd/csrc/table.h pdht_amd/csrc/table_geom.h pdht_amd/csrc/table_host.h pdht_amd/csrc/rows.h
+$(LIBDIR)/pdht_table.o $(LIBDIR)/pdht_table.tun.o: $(TABLE_HDR)
+$(LIBDIR)/pdht_table_iter.o $(LIBDIR)/pdht_table_iter.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_iter.h
+$(LIBDIR)/pdht_table_rmw.o $(LIBDIR)/pdht_table_rmw.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_rmw.h
+$(LIBDIR)/pdht_table_add.o $(LIBDIR)/pdht_table_add.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_add.h
+$(LIBDIR)/pdht_table_reduce.o $(LIBDIR)/pdht_table_reduce.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_acc.h
 $(foreach u,pdht_fixed64 pdht_fixed128 pdht_var pdht_host,$(LIBDIR)/$(u).o $(LIBDIR)/$(u).tun.o): pdht_amd/csrc/launch.h
 $(LIBDIR)/pdht_host.o $(LIBDIR)/pdht_host.tun.o: pdht_amd/csrc/host_chunks.h
 

@@ -1071,26 +1071,68 @@ class DeviceTable:
         dropped; counts()[2] advances by one."""
         return self._apply_records("update", records, status, workspace, stream)
 
-    def _apply_records(self, kind, records, status, workspace, stream):
-        torch = _torch()
+    # The arguments that the records operations share, each checked in one place
+
+    def _records_arg(self, records):
+        """-> (m, row stride in bytes) of a batch of put records."""
         m, B, stride = _rows_2d(records, "records", self.device)
         if B < 24 + self.rowbytes:
             raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
         if stride % 8 or records.data_ptr() % 8:
             raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
+        return m, stride
+
+    def _status_arg(self, status, m):
+        """True -> a new uint8 [m]; False / None -> None; a tensor is checked."""
+        torch = _torch()
         if status is True:
-            status = torch.empty(m, dtype=torch.uint8, device=self.device)
-        elif status is False or status is None:
-            status = None
-        else:
-            _need(status, "status", torch.uint8, self.device, shape=(m,))
-        need = getattr(lib(), f"pdht_table_{kind}_workspace_bytes")(m)
+            return torch.empty(m, dtype=torch.uint8, device=self.device)
+        if status is False or status is None:
+            return None
+        _need(status, "status", torch.uint8, self.device, shape=(m,))
+        return status
+
+    def _replies_arg(self, replies, m):
+        """True -> new head-8 replies; False / None -> None; a tensor is
+        checked.  -> (replies, their row stride in bytes)."""
+        torch = _torch()
+        rb = 8 + self.rowbytes
+        if replies is True:
+            replies = torch.empty((m, rb // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, rb)
+        elif replies is False or replies is None:
+            return None, 0
+        om, oB, rstride = _rows_2d(replies, "replies", self.device)
+        if (om, oB) != (m, rb):
+            raise ValueError(f"replies must have shape [{m}, {rb}], got {tuple(replies.shape)}")
+        if rstride % 8 or replies.data_ptr() % 8:
+            raise ValueError("replies must be 8-byte aligned with a row stride that is a multiple of 8")
+        return replies, rstride
+
+    def _workspace_arg(self, workspace, need):
+        """None -> a new workspace of `need` bytes; a tensor is checked."""
+        torch = _torch()
         if workspace is None:
-            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
-        else:
-            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
-            if workspace.data_ptr() % 4:
-                raise ValueError("workspace must be 4-byte aligned")
+            return torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
+        _need(workspace, "workspace", torch.uint8, self.device, numel=need)
+        if workspace.data_ptr() % 4:
+            raise ValueError("workspace must be 4-byte aligned")
+        return workspace
+
+    def _region_arg(self, size, value_offset, elems):
+        """The region of an accumulate or a reduce inside the row."""
+        for name, v in (("value_offset", value_offset), ("elems", elems)):
+            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
+                raise ValueError(f"{name} must be a non-negative int, got {v!r}")
+        if value_offset % size or elems < 1 or value_offset + elems * size > self.rowbytes:
+            raise ValueError(f"the region must be elems >= 1 elements of {size} bytes at a value_offset that is a "
+                             f"multiple of {size}, inside the {self.rowbytes}-byte row; got value_offset "
+                             f"{value_offset}, elems {elems}")
+
+    def _apply_records(self, kind, records, status, workspace, stream):
+        m, stride = self._records_arg(records)
+        status = self._status_arg(status, m)
+        need = getattr(lib(), f"pdht_table_{kind}_workspace_bytes")(m)
+        workspace = self._workspace_arg(workspace, need)
         with _on(self.device, stream) as g:
             name = f"pdht_table_{kind}_records_dev"
             _check(getattr(lib(), name)(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records), stride, m,
@@ -1122,34 +1164,13 @@ class DeviceTable:
         than 2^53 of them add exactly.  The table must be in ordinary device
         memory.  workspace: uint8, >=
         table_acc_workspace_bytes(m, insert) bytes (allocated if None)."""
-        torch = _torch()
         datatype, size = _acc_datatype(dtype)
-        for name, v in (("value_offset", value_offset), ("elems", elems)):
-            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
-                raise ValueError(f"{name} must be a non-negative int, got {v!r}")
-        if value_offset % size or elems < 1 or value_offset + elems * size > self.rowbytes:
-            raise ValueError(f"the region must be elems >= 1 elements of {size} bytes at a value_offset that is a "
-                             f"multiple of {size}, inside the {self.rowbytes}-byte row; got value_offset "
-                             f"{value_offset}, elems {elems}")
-        m, B, stride = _rows_2d(records, "records", self.device)
-        if B < 24 + self.rowbytes:
-            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
-        if stride % 8 or records.data_ptr() % 8:
-            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
-        if status is True:
-            status = torch.empty(m, dtype=torch.uint8, device=self.device)
-        elif status is False or status is None:
-            status = None
-        else:
-            _need(status, "status", torch.uint8, self.device, shape=(m,))
+        self._region_arg(size, value_offset, elems)
+        m, stride = self._records_arg(records)
+        status = self._status_arg(status, m)
         flags = PDHT_ACC_INSERT if insert else 0
         need = lib().pdht_table_acc_workspace_bytes(m, flags)
-        if workspace is None:
-            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
-        else:
-            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
-            if workspace.data_ptr() % 4:
-                raise ValueError("workspace must be 4-byte aligned")
+        workspace = self._workspace_arg(workspace, need)
         with _on(self.device, stream) as g:
             _check(lib().pdht_table_acc_records_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records),
                                                     stride, m, datatype, PDHT_ACC_ADD, value_offset, elems, flags,
@@ -1181,46 +1202,15 @@ class DeviceTable:
         without replies, (status, replies) with them.  workspace: uint8, >=
         table_reduce_workspace_bytes(m, insert, replies) bytes (allocated if
         None)."""
-        torch = _torch()
         datatype, size = _acc_datatype(dtype)
         op = _red_op(op, dtype)
-        for name, v in (("value_offset", value_offset), ("elems", elems)):
-            if not isinstance(v, int) or isinstance(v, bool) or v < 0:
-                raise ValueError(f"{name} must be a non-negative int, got {v!r}")
-        if value_offset % size or elems < 1 or value_offset + elems * size > self.rowbytes:
-            raise ValueError(f"the region must be elems >= 1 elements of {size} bytes at a value_offset that is a "
-                             f"multiple of {size}, inside the {self.rowbytes}-byte row; got value_offset "
-                             f"{value_offset}, elems {elems}")
-        m, B, stride = _rows_2d(records, "records", self.device)
-        if B < 24 + self.rowbytes:
-            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
-        if stride % 8 or records.data_ptr() % 8:
-            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
-        if status is True:
-            status = torch.empty(m, dtype=torch.uint8, device=self.device)
-        elif status is False or status is None:
-            status = None
-        else:
-            _need(status, "status", torch.uint8, self.device, shape=(m,))
-        rb, rstride = 8 + self.rowbytes, 0
-        if replies is True:
-            replies = torch.empty((m, rb // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, rb)
-        elif replies is False or replies is None:
-            replies = None
-        if replies is not None:
-            om, oB, rstride = _rows_2d(replies, "replies", self.device)
-            if (om, oB) != (m, rb):
-                raise ValueError(f"replies must have shape [{m}, {rb}], got {tuple(replies.shape)}")
-            if rstride % 8 or replies.data_ptr() % 8:
-                raise ValueError("replies must be 8-byte aligned with a row stride that is a multiple of 8")
+        self._region_arg(size, value_offset, elems)
+        m, stride = self._records_arg(records)
+        status = self._status_arg(status, m)
+        replies, rstride = self._replies_arg(replies, m)
         flags = PDHT_ACC_INSERT if insert else 0
         need = lib().pdht_table_reduce_workspace_bytes(m, flags, 1 if replies is not None else 0)
-        if workspace is None:
-            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
-        else:
-            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
-            if workspace.data_ptr() % 4:
-                raise ValueError("workspace must be 4-byte aligned")
+        workspace = self._workspace_arg(workspace, need)
         with _on(self.device, stream) as g:
             _check(lib().pdht_table_reduce_records_dev(_dptr(self.storage), self.capacity, self.rowbytes,
                                                        _dptr(records), stride, m, datatype, op, value_offset, elems,
@@ -1245,36 +1235,11 @@ class DeviceTable:
         for dist.exchange_replies and get_resolve.  Returns status without
         replies, (status, replies) with them.  workspace: uint8, >=
         table_add_workspace_bytes(m) bytes (allocated if None)."""
-        torch = _torch()
-        m, B, stride = _rows_2d(records, "records", self.device)
-        if B < 24 + self.rowbytes:
-            raise ValueError(f"records must have >= {24 + self.rowbytes} bytes per row, got {B}")
-        if stride % 8 or records.data_ptr() % 8:
-            raise ValueError("records must be 8-byte aligned with a row stride that is a multiple of 8")
-        if status is True:
-            status = torch.empty(m, dtype=torch.uint8, device=self.device)
-        elif status is False or status is None:
-            status = None
-        else:
-            _need(status, "status", torch.uint8, self.device, shape=(m,))
-        rb, rstride = 8 + self.rowbytes, 0
-        if replies is True:
-            replies = torch.empty((m, rb // 8), dtype=torch.int64, device=self.device).view(torch.uint8).view(m, rb)
-        elif replies is False or replies is None:
-            replies = None
-        if replies is not None:
-            om, oB, rstride = _rows_2d(replies, "replies", self.device)
-            if (om, oB) != (m, rb):
-                raise ValueError(f"replies must have shape [{m}, {rb}], got {tuple(replies.shape)}")
-            if rstride % 8 or replies.data_ptr() % 8:
-                raise ValueError("replies must be 8-byte aligned with a row stride that is a multiple of 8")
+        m, stride = self._records_arg(records)
+        status = self._status_arg(status, m)
+        replies, rstride = self._replies_arg(replies, m)
         need = lib().pdht_table_add_workspace_bytes(m)
-        if workspace is None:
-            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
-        else:
-            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
-            if workspace.data_ptr() % 4:
-                raise ValueError("workspace must be 4-byte aligned")
+        workspace = self._workspace_arg(workspace, need)
         with _on(self.device, stream) as g:
             _check(lib().pdht_table_add_records_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(records),
                                                     stride, m, _dptr(workspace), workspace.numel(), _opt(status),
@@ -1352,13 +1317,7 @@ class DeviceTable:
             raise ValueError(f"out must have shape [{m}, 16], got {tuple(out.shape)}")
         if ostride % 8 or out.data_ptr() % 8:
             raise ValueError("out must be 8-byte aligned with a row stride that is a multiple of 8")
-        need = lib().pdht_table_cswap_workspace_bytes(m)
-        if workspace is None:
-            workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=self.device).view(torch.uint8)
-        else:
-            _need(workspace, "workspace", torch.uint8, self.device, numel=need)
-            if workspace.data_ptr() % 4:
-                raise ValueError("workspace must be 4-byte aligned")
+        workspace = self._workspace_arg(workspace, lib().pdht_table_cswap_workspace_bytes(m))
         with _on(self.device, stream) as g:
             _check(lib().pdht_table_cswap_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
                                               stride, m, word_offset, pair[0], pair[1], _dptr(out), ostride,

@@ -1,7 +1,6 @@
 // pdht_table.hip -- the device-resident target table and the client's resolve
 // (include/pdht_hip_table.h; kernels in table.h): argument checks, launchers
 // and the C ABI.  Every check runs before any device call.
-#include "table.h"
 #include "table_host.h"
 
 namespace pdht {
@@ -11,15 +10,9 @@ static thread_local char g_table_pair[96];
 static int table_put(void *table, u64 capacity, size_t rowbytes, const void *records, size_t record_stride,
                      size_t m, void *workspace, size_t workspace_bytes, uint8_t *status, hipStream_t st) {
   if (int rc = geom_check(table, capacity, rowbytes)) return rc;
-  if (m >= (1ull << 32)) return fail("table put: m must be < 2^32 per call%s", "");
-  if (record_stride < 24 + rowbytes || (record_stride & 7))
-    return fail("table put: record_stride must be a multiple of 8 and >= 24 + rowbytes%s", "");
-  if ((uintptr_t)records & 7) return fail("table put: records must be 8-byte aligned%s", "");
-  if ((uintptr_t)workspace & 3) return fail("table put: workspace must be 4-byte aligned%s", "");
-  if (workspace_bytes < 4 * m) return fail("table put: workspace too small (%s%lld bytes needed)", "", (long long)(4 * m));
-  if (m && !records) return fail("table put: records must not be NULL%s", "");
-  if (m && !workspace) return fail("table put: workspace must not be NULL%s", "");
-  const bool p16 = (rowbytes & 15) == 0 && (record_stride & 15) == 0 && (((uintptr_t)records + 24) & 15) == 0;
+  if (int rc = records_check("put", rowbytes, records, record_stride, m)) return rc;
+  if (int rc = buffers_check("put", rowbytes, records, m, workspace, workspace_bytes, 4 * m)) return rc;
+  const bool p16 = rows_p16(rowbytes, records, record_stride);
   snprintf(g_table_pair, sizeof g_table_pair, "k_table_claim+k_table_write<%d>", p16 ? 16 : 8);
   g_kernel = g_table_pair;
   if (m == 0) return 0;
@@ -40,15 +33,7 @@ static int table_put(void *table, u64 capacity, size_t rowbytes, const void *rec
   w.m = m;
   w.slots = c.slots;
   w.status = status;
-  w.np = (u32)(rowbytes / (p16 ? 16 : 8));
-  w.gshift = group_shift(w.np);
-  w.absent = 2;
-  const unsigned grid = table_grid(m, (u64)(64u >> w.gshift) * kRowsInFlight, dev);
-  const bool nt = hook_table_put_nt(kTablePutNt);
-  if (p16)
-    nt ? k_table_write<16, true><<<grid, kBlock, 0, st>>>(w) : k_table_write<16, false><<<grid, kBlock, 0, st>>>(w);
-  else
-    nt ? k_table_write<8, true><<<grid, kBlock, 0, st>>>(w) : k_table_write<8, false><<<grid, kBlock, 0, st>>>(w);
+  launch_table_write(w, p16, 2, dev, st);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -1,8 +1,10 @@
-// pdht_table_reduce.hip -- reductions on the entries of the device-resident target table
-// (include/pdht_hip_table_reduce.h; kernels: k_table_acc<T, .., OP> of table_acc.h, k_table_add_reply<W> of
-// table_add.h): argument checks, launcher and the C ABI.  Every check runs before any device call.
+// pdht_table_reduce.hip -- the accumulate and the reductions on the entries of the device-resident target
+// table (include/pdht_hip_table_acc.h, include/pdht_hip_table_reduce.h; kernels: k_table_acc<T, .., OP> of
+// table_acc.h, the replies k_table_get<W, .., slots> of table.h): argument checks, launcher and the C ABI.
+// The accumulate is the reduce with the sum and without replies: one implementation behind both entry points.
+// Every check runs before any device call.
 #include "pdht_hip_table_reduce.h"
-#include "table_add.h"
+#include "table_acc.h"
 #include "table_host.h"
 
 namespace pdht {
@@ -13,15 +15,15 @@ static_assert(PDHT_RED_ADD == kRedAdd && PDHT_RED_MIN == kRedMin && PDHT_RED_MAX
 
 static thread_local char g_red_name[128];
 
-// In-wave combining of the operands that share a slot, as the accumulate's sums (pdht_table_acc.hip)
+// In-wave combining of the operands that share a slot (EXPERIMENTS.md §R12 has the alternative's times)
 constexpr bool kTableRedCombine = true;
 
 static size_t red_workspace(size_t m, unsigned flags, bool replies) {
-  return (flags & PDHT_ACC_INSERT) ? 4 * m + ((m + 3) & ~(size_t)3) : replies ? 4 * m : 0;
+  return (flags & PDHT_ACC_INSERT) ? claim_workspace(m) : replies ? 4 * m : 0;
 }
 
-// As the accumulate: the form without combining exists for the integer types only, no k_table_acc<double, *,
-// false, *> is built for any op (EXPERIMENTS.md §R12)
+// The form without combining exists for the integer types only: no k_table_acc<double, *, false, *> is built
+// for any op (EXPERIMENTS.md §R12: the run that posted one fp64 atomic per record on one word stalled)
 template <class T, bool INSERT, int OP>
 static void red_launch(const AccArgs &a, unsigned grid, hipStream_t st) {
   if constexpr (std::is_same<T, double>::value) {
@@ -56,42 +58,34 @@ static void red_op(int op, const AccArgs &a, unsigned grid, hipStream_t st) {
   }
 }
 
-static int table_reduce(void *table, u64 capacity, size_t rowbytes, const void *records, size_t record_stride,
-                        size_t m, int datatype, int op, size_t value_offset, size_t elems, unsigned flags,
-                        void *workspace, size_t workspace_bytes, uint8_t *status, void *replies, size_t reply_stride,
-                        hipStream_t st) {
+// acc: the call came in as pdht_table_acc_records_dev -- its own name in the messages, no op but the sum, no replies
+static int table_reduce(bool acc, void *table, u64 capacity, size_t rowbytes, const void *records,
+                        size_t record_stride, size_t m, int datatype, int op, size_t value_offset, size_t elems,
+                        unsigned flags, void *workspace, size_t workspace_bytes, uint8_t *status, void *replies,
+                        size_t reply_stride, hipStream_t st) {
+  const char *name = acc ? "acc" : "reduce";
   if (int rc = geom_check(table, capacity, rowbytes)) return rc;
-  if (m >= (1ull << 32)) return fail("table reduce: m must be < 2^32 per call%s", "");
-  if (record_stride < 24 + rowbytes || (record_stride & 7))
-    return fail("table reduce: record_stride must be a multiple of 8 and >= 24 + rowbytes%s", "");
-  if ((uintptr_t)records & 7) return fail("table reduce: records must be 8-byte aligned%s", "");
+  if (int rc = records_check(name, rowbytes, records, record_stride, m)) return rc;
   if (datatype != PDHT_ACC_INT32 && datatype != PDHT_ACC_INT64 && datatype != PDHT_ACC_DOUBLE)
-    return fail("table reduce: datatype must be PDHT_ACC_INT32, PDHT_ACC_INT64 or PDHT_ACC_DOUBLE%s", "");
-  if (op < PDHT_RED_ADD || op > PDHT_RED_XOR) return fail("table reduce: op must be PDHT_RED_ADD .. PDHT_RED_XOR%s", "");
+    return fail("table %s: datatype must be PDHT_ACC_INT32, PDHT_ACC_INT64 or PDHT_ACC_DOUBLE", name);
+  if (acc && op != PDHT_ACC_ADD) return fail("table acc: op must be PDHT_ACC_ADD");
+  if (op < PDHT_RED_ADD || op > PDHT_RED_XOR) return fail("table reduce: op must be PDHT_RED_ADD .. PDHT_RED_XOR");
   if (datatype == PDHT_ACC_DOUBLE && op >= PDHT_RED_AND)
-    return fail("table reduce: PDHT_RED_AND, _OR and _XOR are not defined for PDHT_ACC_DOUBLE%s", "");
-  if (flags & ~PDHT_ACC_INSERT) return fail("table reduce: unknown flags%s", "");
+    return fail("table reduce: PDHT_RED_AND, _OR and _XOR are not defined for PDHT_ACC_DOUBLE");
+  if (flags & ~PDHT_ACC_INSERT) return fail("table %s: unknown flags", name);
   const size_t size = datatype == PDHT_ACC_INT32 ? 4 : 8;
-  if (value_offset % size) return fail("table reduce: value_offset must be a multiple of the element size%s", "");
+  if (value_offset % size) return fail("table %s: value_offset must be a multiple of the element size", name);
   // (rowbytes < 2^31: neither the division nor the sum can wrap)
   if (elems == 0 || value_offset > rowbytes || elems > (rowbytes - value_offset) / size)
-    return fail("table reduce: elems must be >= 1 and value_offset + elems * size <= rowbytes%s", "");
+    return fail("table %s: elems must be >= 1 and value_offset + elems * size <= rowbytes", name);
   const bool insert = (flags & PDHT_ACC_INSERT) != 0;
   const size_t need = red_workspace(m, flags, replies != nullptr);
-  if (need && ((uintptr_t)workspace & 3)) return fail("table reduce: workspace must be 4-byte aligned%s", "");
-  if (workspace_bytes < need)
-    return fail("table reduce: workspace too small (%s%lld bytes needed)", "", (long long)need);
-  if (replies) {  // (without replies the stride means nothing)
-    if ((uintptr_t)replies & 7) return fail("table reduce: replies must be 8-byte aligned%s", "");
-    if (reply_stride < 8 + rowbytes || (reply_stride & 7))
-      return fail("table reduce: reply_stride must be a multiple of 8 and >= 8 + rowbytes%s", "");
-  }
-  if (m && !records) return fail("table reduce: records must not be NULL%s", "");
-  if (need && !workspace) return fail("table reduce: workspace must not be NULL%s", "");
+  if (int rc = buffers_check(name, rowbytes, records, m, need ? workspace : nullptr, workspace_bytes, need, replies,
+                             reply_stride))
+    return rc;
   static const char *const kOps[] = {"", ",min", ",max", ",and", ",or", ",xor"};
   const char *ty = datatype == PDHT_ACC_INT32 ? "i32" : datatype == PDHT_ACC_INT64 ? "i64" : "f64";
-  const u32 nw = (u32)(rowbytes / 8) + 1;  // the get's piece rule for the replies
-  const bool w2 = replies && (((uintptr_t)replies | reply_stride) & 15) == 0 && (nw & 1) == 0;
+  const bool w2 = replies_w2(rowbytes, replies, reply_stride);
   int n = snprintf(g_red_name, sizeof g_red_name, insert ? "k_table_acc_claim+k_table_acc<%s%s,insert>" : "k_table_acc<%s%s>",
                    ty, kOps[op]);
   if (replies) snprintf(g_red_name + n, sizeof g_red_name - n, "+k_table_add_reply<%d>", w2 ? 16 : 8);
@@ -138,23 +132,7 @@ static int table_reduce(void *table, u64 capacity, size_t rowbytes, const void *
     insert ? red_op<double, true>(op, a, grid, st) : red_op<double, false>(op, a, grid, st);
   HIP_TRY(hipGetLastError());
   if (!replies) return 0;
-  // behind k_table_acc no kernel of the call writes a row: plain loads of the reduced rows
-  AddReplyArgs r{};
-  r.t = a.t;
-  r.slots = slots;
-  r.m = m;
-  r.replies = static_cast<uint8_t *>(replies);
-  r.reply_stride = reply_stride;
-  r.np = w2 ? nw / 2 : nw;
-  r.gshift = group_shift(r.np);
-  const unsigned rgrid = table_grid(m, 64u >> r.gshift, dev);
-  const bool reply_nt = hook_table_reply_nt(kTableReplyNt);
-  if (w2)
-    reply_nt ? k_table_add_reply<2, true><<<rgrid, kBlock, 0, st>>>(r)
-             : k_table_add_reply<2, false><<<rgrid, kBlock, 0, st>>>(r);
-  else
-    reply_nt ? k_table_add_reply<1, true><<<rgrid, kBlock, 0, st>>>(r)
-             : k_table_add_reply<1, false><<<rgrid, kBlock, 0, st>>>(r);
+  launch_table_reply(a.t, slots, m, replies, reply_stride, w2, dev, st);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -162,6 +140,16 @@ static int table_reduce(void *table, u64 capacity, size_t rowbytes, const void *
 }  // namespace pdht
 
 using namespace pdht;
+
+PDHT_API size_t pdht_table_acc_workspace_bytes(size_t m, unsigned flags) { return red_workspace(m, flags, false); }
+
+PDHT_API int pdht_table_acc_records_dev(void *table, uint64_t capacity, size_t rowbytes, const void *records,
+                                        size_t record_stride, size_t m, int datatype, int op, size_t value_offset,
+                                        size_t elems, unsigned flags, void *workspace, size_t workspace_bytes,
+                                        uint8_t *status, pdht_hip_stream_t s) {
+  return table_reduce(true, table, capacity, rowbytes, records, record_stride, m, datatype, op, value_offset, elems,
+                      flags, workspace, workspace_bytes, status, nullptr, 0, ST(s));
+}
 
 PDHT_API size_t pdht_table_reduce_workspace_bytes(size_t m, unsigned flags, int with_replies) {
   return red_workspace(m, flags, with_replies != 0);
@@ -171,6 +159,6 @@ PDHT_API int pdht_table_reduce_records_dev(void *table, uint64_t capacity, size_
                                            size_t record_stride, size_t m, int datatype, int op, size_t value_offset,
                                            size_t elems, unsigned flags, void *workspace, size_t workspace_bytes,
                                            uint8_t *status, void *replies, size_t reply_stride, pdht_hip_stream_t s) {
-  return table_reduce(table, capacity, rowbytes, records, record_stride, m, datatype, op, value_offset, elems, flags,
-                      workspace, workspace_bytes, status, replies, reply_stride, ST(s));
+  return table_reduce(false, table, capacity, rowbytes, records, record_stride, m, datatype, op, value_offset, elems,
+                      flags, workspace, workspace_bytes, status, replies, reply_stride, ST(s));
 }

@@ -33,7 +33,7 @@ static inline bool hook_table_reply_nt(bool dflt) { return dflt; }
 static inline bool hook_table_put_nt(bool dflt) { return dflt; }
 // pdht_table_iter.hip: non-temporal stores of an export's mbits, slot indices and rows
 static inline bool hook_table_export_nt(bool dflt) { return dflt; }
-// pdht_table_acc.hip: in-wave sums of the addends of one slot ahead of the atomics
+// pdht_table_reduce.hip: in-wave sums of the addends of one slot ahead of the atomics
 static inline bool hook_table_acc_combine(bool dflt) { return dflt; }
 
 }  // namespace pdht

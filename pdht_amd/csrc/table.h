@@ -22,6 +22,11 @@
 // tag that is there, and the probe goes on from that value; a non-empty tag is
 // final.  So no lane waits for another: every loop counts down from C.
 //
+// What the operations share is here: table_find (the probe that inserts nothing), table_claim (the probe
+// that claims an empty slot, with table_count for the counters), table_win_post (the winner word of a slot,
+// one atomicMax per slot and wave), k_table_write (the rows of a put or an update) and k_table_get (the
+// replies of a get, and on the slots of a workspace those of an insert-if-absent or a reduce).
+//
 // put = two kernels, the kernel boundary their only synchronisation:
 //   k_table_claim  one lane per record: probe, claim when new, atomicMax the
 //                  slot's winner word with (batch << 32) | position, slot -> workspace.
@@ -57,6 +62,80 @@ __device__ __forceinline__ u32 wave_sum(u32 v) {
   return v;
 }
 
+__device__ __forceinline__ u32 wave_max(u32 v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor(v, o));
+  return v;
+}
+
+// The inserting probe of the put, the insert-if-absent and the inserting accumulate: the slot that holds
+// mb, claimed when no slot held it, or kTableNoSlot when the table is full.  made: this lane's CAS created
+// the tag.  n_seen counts the slots inspected.  Every lane may call it with its own mb.
+__device__ __forceinline__ u32 table_claim(const TableGeom &t, u64 mb, bool &made, u32 &n_seen) {
+  made = false;
+  if (mb == 0) {
+    ++n_seen;
+    made = tag_load(t.tags + t.cap) == 0 && atomicCAS((unsigned long long *)(t.tags + t.cap), 0ull, 1ull) == 0;
+    return t.cap;
+  }
+  u64 h = (mb * kTableMix) >> t.shift;
+  for (u64 left = t.mask + 1; left; --left) {
+    h &= t.mask;
+    ++n_seen;
+    u64 tag = tag_load(t.tags + h);
+    if (tag == 0) {
+      tag = atomicCAS((unsigned long long *)(t.tags + h), 0ull, (unsigned long long)mb);
+      if (tag == 0) {
+        made = true;
+        tag = mb;
+      }
+    }
+    if (tag == mb) return (u32)h;
+    ++h;
+  }
+  return kTableNoSlot;
+}
+
+// A claim kernel's counts (entries made, records dropped, slots inspected) into the table's counters: one
+// atomic per wave per counter.  Whole waves call it.
+__device__ __forceinline__ void table_count(const TableGeom &t, u32 n_new, u32 n_drop, u32 n_seen) {
+  n_new = wave_sum(n_new), n_drop = wave_sum(n_drop), n_seen = wave_sum(n_seen);
+  if ((threadIdx.x & 63) == 0) {
+    if (n_new) atomicAdd((unsigned long long *)(t.counters + 0), (unsigned long long)n_new);
+    if (n_drop) atomicAdd((unsigned long long *)(t.counters + 1), (unsigned long long)n_drop);
+    if (n_seen) atomicAdd((unsigned long long *)(t.counters + 3), (unsigned long long)n_seen);
+  }
+}
+
+// The winner word of `slot` takes batch | rank of position p: the FIRST position of a slot wins with rank
+// 0xFFFFFFFF - p, the last with rank p.  Whole waves call it, a lane without a slot with kTableNoSlot.
+// Lanes of a wave that found the same slot post one atomicMax between them: a batch whose requests pile
+// up on one mbits (every claimant of a hot k-mer) would otherwise queue one atomic per request on one
+// word (EXPERIMENTS.md §R11).  Two leaders are tried -- the first lane that has a slot, then the first
+// lane outside its group -- and every lane left over posts its own.  The maximum of a group's ranks is
+// what its atomics would have left, so the winner word ends the same.
+constexpr int kLocateLeaders = 2;
+
+template <bool FIRST>
+__device__ __forceinline__ void table_win_post(const TableGeom &t, u32 slot, u64 p, u64 batch, u32 lane) {
+  const u32 rank = FIRST ? 0xFFFFFFFFu - (u32)p : (u32)p;
+  bool todo = slot != kTableNoSlot, cand = todo;
+#pragma unroll
+  for (int k = 0; k < kLocateLeaders; ++k) {
+    const u64 open = __ballot(cand);
+    if (!open) break;  // (wave-uniform)
+    const u32 leader = (u32)__ffsll((unsigned long long)open) - 1;
+    const u32 s = (u32)__shfl((int)slot, (int)leader);
+    const bool mine = cand && slot == s;
+    cand = cand && !mine;
+    if (__popcll(__ballot(mine)) < 2) continue;  // (wave-uniform) the leader stands alone: its own atomic below
+    const u32 best = wave_max(mine ? rank : 0u);
+    if (lane == leader) atomicMax((unsigned long long *)(t.win + s), (unsigned long long)(batch | best));
+    todo = todo && !mine;
+  }
+  if (todo) atomicMax((unsigned long long *)(t.win + slot), (unsigned long long)(batch | rank));
+}
+
 struct ClaimArgs {
   TableGeom t;
   const uint8_t *records;
@@ -65,7 +144,7 @@ struct ClaimArgs {
   u32 *slots;
 };
 
-// (static: table.h is part of two translation units, pdht_table.hip and pdht_table_rmw.hip)
+// (static: table.h is part of several translation units)
 static __global__ __launch_bounds__(kBlock) void k_table_claim(const ClaimArgs a) {
   const TableGeom &t = a.t;
   const u64 batch = t.counters[2] << 32;  // (only k_table_write of the same call, behind this kernel, writes it)
@@ -75,43 +154,15 @@ static __global__ __launch_bounds__(kBlock) void k_table_claim(const ClaimArgs a
   u64 p = (u64)blockIdx.x * kBlock + threadIdx.x;
   for (u64 r = 0; r < rounds; ++r, p += nthreads) {
     if (p >= a.m) continue;
-    const u64 mb = *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16);
-    u32 slot = kTableNoSlot;
-    if (mb == 0) {
-      ++n_seen;
-      slot = t.cap;
-      if (tag_load(t.tags + t.cap) == 0 && atomicCAS((unsigned long long *)(t.tags + t.cap), 0ull, 1ull) == 0) ++n_new;
-    } else {
-      u64 h = (mb * kTableMix) >> t.shift;
-      for (u64 left = t.mask + 1; left; --left) {
-        h &= t.mask;
-        ++n_seen;
-        u64 tag = tag_load(t.tags + h);
-        if (tag == 0) {
-          tag = atomicCAS((unsigned long long *)(t.tags + h), 0ull, (unsigned long long)mb);
-          if (tag == 0) {
-            ++n_new;
-            tag = mb;
-          }
-        }
-        if (tag == mb) {
-          slot = (u32)h;
-          break;
-        }
-        ++h;
-      }
-      if (slot == kTableNoSlot) ++n_drop;
-    }
+    bool made;
+    const u32 slot = table_claim(t, *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16), made, n_seen);
+    n_new += made;
+    n_drop += slot == kTableNoSlot;
+    // the LAST position, one atomic per record (no leaders: table_win_post needs whole waves)
     if (slot != kTableNoSlot) atomicMax((unsigned long long *)(t.win + slot), (unsigned long long)(batch | p));
     a.slots[p] = slot;
   }
-  // one atomic per wave per counter
-  n_new = wave_sum(n_new), n_drop = wave_sum(n_drop), n_seen = wave_sum(n_seen);
-  if ((threadIdx.x & 63) == 0) {
-    if (n_new) atomicAdd((unsigned long long *)(t.counters + 0), (unsigned long long)n_new);
-    if (n_drop) atomicAdd((unsigned long long *)(t.counters + 1), (unsigned long long)n_drop);
-    if (n_seen) atomicAdd((unsigned long long *)(t.counters + 3), (unsigned long long)n_seen);
-  }
+  table_count(t, n_new, n_drop, n_seen);
 }
 
 struct WriteArgs {
@@ -176,7 +227,8 @@ __global__ __launch_bounds__(kBlock) void k_table_write(const WriteArgs a) {
 
 struct GetArgs {
   TableGeom t;
-  const uint8_t *mbits;
+  const uint8_t *mbits;  // the requests, or
+  const u32 *slots;      // SLOTS: every request's slot or kTableNoSlot, as a claim or locate kernel left it
   u64 mbits_stride;
   u64 m;
   uint8_t *replies;
@@ -190,7 +242,9 @@ struct GetArgs {
 // moves W = 1 or 2 of them (2: one 16-byte store).  Every lane of a group probes for its request (one
 // address per group: the wave's load merges them); the row words are loaded without a branch (of slot 0
 // when there is no row) ahead of the predicated stores.
-template <int W, bool NT>
+// SLOTS: the replies of the insert-if-absent and of the reduce ("k_table_add_reply<W>" in last_kernel), whose
+// first kernel left every record's slot in the workspace: no probe, no tag line is touched.
+template <int W, bool NT, bool SLOTS = false>
 __global__ __launch_bounds__(kBlock) void k_table_get(const GetArgs a) {
   const TableGeom &t = a.t;
   const u32 lane = threadIdx.x & 63;
@@ -200,9 +254,12 @@ __global__ __launch_bounds__(kBlock) void k_table_get(const GetArgs a) {
   const u64 last = a.m - 1;
   const u32 nw = (u32)(t.rowbytes >> 3) + 1;
   for (u64 base = wave * rpi; base < a.m; base += nwaves * rpi) {
-    const u64 p = base + g;
-    const u64 mb = *reinterpret_cast<const u64 *>(a.mbits + (p < last ? p : last) * a.mbits_stride);
-    const u32 slot = table_find(t, mb);
+    const u64 p = base + g, pc = p < last ? p : last;
+    u32 slot;
+    if constexpr (SLOTS)
+      slot = a.slots[pc];
+    else
+      slot = table_find(t, *reinterpret_cast<const u64 *>(a.mbits + pc * a.mbits_stride));
     const bool found = slot != kTableNoSlot;
     const u64 *row = reinterpret_cast<const u64 *>(t.rows + (u64)(found ? slot : 0) * t.rowbytes);
     for (u32 c = l; c < a.np; c += 64) {

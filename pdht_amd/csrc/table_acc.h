@@ -6,9 +6,9 @@
 //   flags 0   k_table_acc<T>          a lane group per record: table_find, then device-scope atomic adds
 //                                     of the record's region into the row's, then the status byte.
 //                                     No winner words, no counters: one kernel.
-//   INSERT    k_table_acc_claim       one lane per record: k_table_claim's probe and counters; the
-//                                     winner word takes the FIRST position (0xFFFFFFFF - p, as
-//                                     k_table_locate<first>); the lane whose CAS created the tag marks
+//   INSERT    k_table_acc_claim       one lane per record: table_claim's probe and table_count's counters;
+//                                     the winner word takes the FIRST position (table_win_post<true>:
+//                                     0xFFFFFFFF - p); the lane whose CAS created the tag marks
 //                                     its record as the creator and zeroes the region of the new row
 //                                     (no other lane touches that row in this kernel).
 //             k_table_acc<T, insert>  every record with a slot adds as above; the creator's group reads
@@ -21,7 +21,7 @@
 // result.  Double sums depend on the order the schedule picks (pdht_hip_table_acc.h has the bound).
 //
 // Lanes of a wave whose records found the same slot add their addends together first and post one
-// atomic per element between them -- k_table_locate's leader scheme with a sum in place of the
+// atomic per element between them -- table_win_post's leader scheme with a sum in place of the
 // maximum: a hot mbits would otherwise queue one atomic per record on one word.
 //
 // OP (include/pdht_hip_table_reduce.h) puts another operation in the place of the sum: min and max
@@ -30,12 +30,12 @@
 // result for every type.  The kernels are the same ones: the in-wave fold uses the op in place of +=, lanes
 // without an operand feed its identity, the post is one integer atomic per element, and INSERT starts a new
 // row's region from the identity where the sum starts it from zero.  None of them is an fp atomic.
-// For replies (k_table_add_reply of table_add.h, a launch behind these) the flags-0 kernel also stores every
+// For replies (k_table_get<W, .., slots> of table.h, a launch behind these) the flags-0 kernel also stores every
 // record's slot to the workspace, where k_table_acc_claim leaves it under INSERT.
 #pragma once
 #include <limits>
 
-#include "table_rmw.h"
+#include "table.h"
 
 namespace pdht {
 
@@ -243,34 +243,10 @@ static __global__ __launch_bounds__(kBlock) void k_table_acc_claim(const AccClai
   for (u64 r = 0; r < rounds; ++r, p += nthreads) {
     u32 slot = kTableNoSlot;
     if (p < a.m) {
-      const u64 mb = *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16);
-      bool made = false;
-      if (mb == 0) {
-        ++n_seen;
-        slot = t.cap;
-        made = tag_load(t.tags + t.cap) == 0 && atomicCAS((unsigned long long *)(t.tags + t.cap), 0ull, 1ull) == 0;
-      } else {
-        u64 h = (mb * kTableMix) >> t.shift;
-        for (u64 left = t.mask + 1; left; --left) {
-          h &= t.mask;
-          ++n_seen;
-          u64 tag = tag_load(t.tags + h);
-          if (tag == 0) {
-            tag = atomicCAS((unsigned long long *)(t.tags + h), 0ull, (unsigned long long)mb);
-            if (tag == 0) {
-              made = true;
-              tag = mb;
-            }
-          }
-          if (tag == mb) {
-            slot = (u32)h;
-            break;
-          }
-          ++h;
-        }
-        if (slot == kTableNoSlot) ++n_drop;
-      }
+      bool made;
+      slot = table_claim(t, *reinterpret_cast<const u64 *>(a.records + p * a.record_stride + 16), made, n_seen);
       n_new += made;
+      n_drop += slot == kTableNoSlot;
       a.slots[p] = slot;
       a.creator[p] = made;
       if (made) {  // a new entry starts from the op's identity, the sums from zero: every record of it
@@ -279,32 +255,9 @@ static __global__ __launch_bounds__(kBlock) void k_table_acc_claim(const AccClai
         for (u64 c = 0; c < a.region_words; ++c) z[c] = a.fill[c & 1];
       }
     }
-    // the first position into the winner word, one atomicMax per slot and wave where lanes share a slot
-    // (k_table_locate<true>'s scheme)
-    const u32 rank = 0xFFFFFFFFu - (u32)p;
-    bool todo = slot != kTableNoSlot, cand = todo;
-#pragma unroll
-    for (int k = 0; k < kLocateLeaders; ++k) {
-      const u64 open = __ballot(cand);
-      if (!open) break;  // (wave-uniform)
-      const u32 leader = (u32)__ffsll((unsigned long long)open) - 1;
-      const u32 s = (u32)__shfl((int)slot, (int)leader);
-      const bool mine = cand && slot == s;
-      cand = cand && !mine;
-      if (__popcll(__ballot(mine)) < 2) continue;  // (wave-uniform) the leader stands alone: its own atomic below
-      const u32 best = wave_max(mine ? rank : 0u);
-      if (lane == leader) atomicMax((unsigned long long *)(t.win + s), (unsigned long long)(batch | best));
-      todo = todo && !mine;
-    }
-    if (todo) atomicMax((unsigned long long *)(t.win + slot), (unsigned long long)(batch | rank));
+    table_win_post<true>(t, slot, p, batch, lane);  // the first position
   }
-  // one atomic per wave per counter
-  n_new = wave_sum(n_new), n_drop = wave_sum(n_drop), n_seen = wave_sum(n_seen);
-  if (lane == 0) {
-    if (n_new) atomicAdd((unsigned long long *)(t.counters + 0), (unsigned long long)n_new);
-    if (n_drop) atomicAdd((unsigned long long *)(t.counters + 1), (unsigned long long)n_drop);
-    if (n_seen) atomicAdd((unsigned long long *)(t.counters + 3), (unsigned long long)n_seen);
-  }
+  table_count(t, n_new, n_drop, n_seen);
 }
 
 struct AccArgs {
@@ -318,7 +271,7 @@ struct AccArgs {
   u64 value_offset;        // of the region inside a row (a multiple of sizeof(T))
   u64 elems;               // elements of T in the region
   u32 gshift;              // log2 of the lane group (G = the power of two >= elems, at most 64)
-  u32 *slot_out;           // flags 0, may be null: every record's slot or kTableNoSlot, for k_table_add_reply
+  u32 *slot_out;           // flags 0, may be null: every record's slot or kTableNoSlot, for the reply kernel
 };
 
 // T: u32, u64 (two's complement sums of either signedness) or double.  A group of G lanes per record,

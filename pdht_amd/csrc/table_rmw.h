@@ -8,8 +8,8 @@
 // polls or waits on another lane), with the put's winner words between them:
 //   k_table_locate<FIRST>  one lane per record: table_find (no CAS: nothing is inserted), the slot ->
 //                          workspace, and on a hit atomicMax of the slot's winner word with
-//                          (batch << 32) | (FIRST ? 0xFFFFFFFF - position : position); lanes of a wave
-//                          with one slot post their maximum once.
+//                          (batch << 32) | (FIRST ? 0xFFFFFFFF - position : position), through
+//                          table_win_post of table.h: lanes of a wave with one slot post their maximum once.
 //                          batch = counters[2] as the call found it, as in k_table_claim: winner words
 //                          of earlier puts, updates and swaps always lose and are never cleared.
 //   update:  k_table_write (table.h) with status 3 for a record without a slot: the LAST record of an
@@ -29,19 +29,6 @@ struct LocateArgs {
   u32 *slots;
 };
 
-__device__ __forceinline__ u32 wave_max(u32 v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v = max(v, (u32)__shfl_xor(v, o));
-  return v;
-}
-
-// Lanes of a wave that found the same slot post one atomicMax between them: a batch whose requests pile
-// up on one mbits (every claimant of a hot k-mer) would otherwise queue one atomic per request on one
-// word (EXPERIMENTS.md §R11).  Two leaders are tried -- the first lane that has a slot, then the first
-// lane outside its group -- and every lane left over posts its own.  The maximum of a group's ranks is
-// what its atomics would have left, so the winner word ends the same.
-constexpr int kLocateLeaders = 2;
-
 template <bool FIRST>
 __global__ __launch_bounds__(kBlock) void k_table_locate(const LocateArgs a) {
   const TableGeom &t = a.t;
@@ -56,22 +43,7 @@ __global__ __launch_bounds__(kBlock) void k_table_locate(const LocateArgs a) {
       slot = table_find(t, *reinterpret_cast<const u64 *>(a.mbits + p * a.mbits_stride));
       a.slots[p] = slot;
     }
-    const u32 rank = FIRST ? 0xFFFFFFFFu - (u32)p : (u32)p;
-    bool todo = slot != kTableNoSlot, cand = todo;
-#pragma unroll
-    for (int k = 0; k < kLocateLeaders; ++k) {
-      const u64 open = __ballot(cand);
-      if (!open) break;  // (wave-uniform)
-      const u32 leader = (u32)__ffsll((unsigned long long)open) - 1;
-      const u32 s = (u32)__shfl((int)slot, (int)leader);
-      const bool mine = cand && slot == s;
-      cand = cand && !mine;
-      if (__popcll(__ballot(mine)) < 2) continue;  // (wave-uniform) the leader stands alone: its own atomic below
-      const u32 best = wave_max(mine ? rank : 0u);
-      if (lane == leader) atomicMax((unsigned long long *)(t.win + s), (unsigned long long)(batch | best));
-      todo = todo && !mine;
-    }
-    if (todo) atomicMax((unsigned long long *)(t.win + slot), (unsigned long long)(batch | rank));
+    table_win_post<FIRST>(t, slot, p, batch, lane);
   }
 }
 
