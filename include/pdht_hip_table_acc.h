@@ -34,8 +34,9 @@
  *                     counts4[0], [1] and [3] advance as a put advances them,
  *                     and counts4[2] by one: the call takes a batch number
  *                     ("batches that used the winner words": put, update,
- *                     cswap, the inserting accumulate and the add of
- *                     pdht_hip_table_add.h).
+ *                     cswap, the inserting accumulate, the add of
+ *                     pdht_hip_table_add.h and the keyed put of
+ *                     pdht_hip_table_keys.h).
  * The region is `elems` elements of `datatype` at value_offset inside the row,
  * at the same place in the record's row (record + 24) and in the table's row.
  *

@@ -36,7 +36,7 @@ __all__ = [
     "device_count", "PdhtTable", "K2", "bucket_batch", "bucket_records", "record_fields",
     "bucket_record_bytes", "bucket_workspace_bytes", "WeakHashLen32WithSeeds", "WeakHashLen32WithSeeds6",
     "tuning", "last_kernel", "mpi_lib", "table_bytes", "table_reply_bytes", "DeviceTable", "get_resolve",
-    "table_export_workspace_bytes", "table_reduce_workspace_bytes",
+    "table_export_workspace_bytes", "table_reduce_workspace_bytes", "table_put_keys_workspace_bytes",
 ]
 
 K2 = 0x9AE16A3B2F90404F  # city.c:96 (CityHash64WithSeed's seed0)
@@ -153,6 +153,9 @@ def _declare(L, tuning=False):
         "pdht_table_reduce_records_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, C.c_int, C.c_int, _S, _S, C.c_uint, _V,
                                                     _S, _V, _V, _S, _V]),
         "pdht_get_resolve_dev": (C.c_int, [_V, _S, _S, _S, _V, _S, _V, _S, _S, _V, _S, _S, _V, _V]),
+        "pdht_table_put_keys_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_put_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _S, _V, _S, _V, _V, _V]),
+        "pdht_table_get_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _S, _V, _S, _S, _V, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
         "CityHash64WithSeeds": (_U64, [_V, _S, _U64, _U64]),
@@ -914,6 +917,9 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   reduce: bucket_put_records -> dist.exchange_records -> DeviceTable.reduce_records(op, replies=True)
 #        -> dist.exchange_replies -> get_resolve(replies, keys, E, index=...)
 #   (include/pdht_hip_table_reduce.h: min, max, and, or, xor beside the sum)
+#   local: DeviceTable.put_keys(keys, values) / DeviceTable.get_keys(keys, E) -- keys and values already on
+#        the table's device: no records, no replies, no sort
+#   (include/pdht_hip_table_keys.h: byte for byte the put and the get flow at nranks = 1)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -962,6 +968,13 @@ def table_add_workspace_bytes(m: int) -> int:
     if not 0 <= m < (1 << 32):
         raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
     return lib().pdht_table_add_workspace_bytes(m)
+
+
+def table_put_keys_workspace_bytes(m: int) -> int:
+    """Bytes of workspace DeviceTable.put_keys needs for m keys: 4*m."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_put_keys_workspace_bytes(m)
 
 
 # the reduce's operations (include/pdht_hip_table_reduce.h)
@@ -1324,6 +1337,93 @@ class DeviceTable:
                                               _dptr(workspace), workspace.numel(), g.stream), "pdht_table_cswap_dev")
         return out
 
+    # ---- put and get by key (include/pdht_hip_table_keys.h) ----
+
+    def _keys_arg(self, keys, elemsize, key_slot):
+        """-> (m, keysize) of a batch of packed keys whose rows of `elemsize`
+        value bytes behind a key slot are this table's rows."""
+        m, L, kstride = _keys_2d(keys)
+        if keys.device != self.device or kstride != L:
+            raise ValueError(f"keys must be packed and on {self.device}")
+        if not 1 <= L <= 64:
+            raise ValueError(f"keys must have 1 .. 64 bytes, got {L}: longer keys go through bucket_put_records "
+                             "and put_records (get: bucket_records, get, get_resolve)")
+        if not isinstance(elemsize, int) or isinstance(elemsize, bool) or elemsize < 1:
+            raise ValueError("elemsize must be >= 1")
+        if not isinstance(key_slot, int) or isinstance(key_slot, bool) or key_slot < 0 or \
+                (key_slot and (key_slot % 8 or key_slot < L)):
+            raise ValueError(f"key_slot {key_slot} must be 0 or a multiple of 8 that is >= keysize {L}")
+        slot = key_slot if key_slot else (L + 7) // 8 * 8
+        if self.rowbytes != (slot + elemsize + 7) // 8 * 8:
+            raise ValueError(f"rowbytes {self.rowbytes} must be the key slot {slot} + elemsize {elemsize} rounded up "
+                             f"to 8 (put_record_bytes(keysize, elemsize, key_slot) - 24)")
+        return m, L
+
+    def _mbits_arg(self, mbits, m):
+        """True -> a new int64 [m]; False / None -> None; a tensor is checked."""
+        torch = _torch()
+        if mbits is True:
+            return torch.empty(m, dtype=torch.int64, device=self.device)
+        if mbits is False or mbits is None:
+            return None
+        return _need(mbits, "mbits", torch.int64, self.device, shape=(m,))
+
+    def put_keys(self, keys, values, *, key_slot: int = 0, status=True, mbits=None, workspace=None, stream=None):
+        """Stores values[i] under keys[i] (pdht_table_put_keys_dev): what
+        bucket_put_records(keys, values, nranks=1, key_slot=key_slot) ->
+        put_records leaves, table, status and counts()[:3] byte for byte,
+        without records: mbits = CityHash64(key), the row is the key, zeros up
+        to the key slot, the value, zeros up to 8, and the last key of an
+        mbits leaves its row.  keys [m, L] packed uint8, L in 1 .. 64; values
+        [m, E] uint8, a row-strided view at any address is accepted; rowbytes
+        must be slot + E rounded up to 8.  status as put_records (0 stored / 1
+        superseded / 2 dropped).  mbits: None / False = none; True = a new
+        int64 [m], a tensor = filled: the digests, for a later get or cswap by
+        mbits.  Returns status, or (status, mbits) with mbits.  workspace:
+        uint8, >= table_put_keys_workspace_bytes(m) bytes (allocated if None).
+        counts()[2] advances by one."""
+        nv, E, vstride = _rows_2d(values, "values", self.device)
+        m, L = self._keys_arg(keys, E, key_slot)
+        if nv != m:
+            raise ValueError(f"values must have one row per key: {nv} rows for {m} keys")
+        status = self._status_arg(status, m)
+        mbits = self._mbits_arg(mbits, m)
+        workspace = self._workspace_arg(workspace, lib().pdht_table_put_keys_workspace_bytes(m))
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_put_keys_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(keys), L,
+                                                 key_slot, _dptr(values), E, vstride, m, _dptr(workspace),
+                                                 workspace.numel(), _opt(mbits), _opt(status), g.stream),
+                   "pdht_table_put_keys_dev")
+        return status if mbits is None else (status, mbits)
+
+    def get_keys(self, keys, elemsize: int, *, key_slot: int = 0, values=None, status=None, mbits=None, stream=None):
+        """Reads the values under keys (pdht_table_get_keys_dev): what
+        bucket_records(keys, 1) -> get -> get_resolve(replies, keys, elemsize,
+        key_slot=key_slot) leaves, without records or replies.  status[i] = 2
+        no entry / 3 collision (the row's key differs from keys[i]) / 0 found,
+        and values[i] receives the row's value when 0.  Returns (values uint8
+        [m, elemsize], status uint8 [m]); rows whose status is not 0 keep their
+        bytes (new values start as zeros, new status as 2).  values may be a
+        row-strided view at any address.  mbits: an int64 [m] tensor receives
+        the digests.  Repeated keys are allowed; the table is not written."""
+        torch = _torch()
+        m, L = self._keys_arg(keys, elemsize, key_slot)
+        if values is None:
+            values = torch.zeros((m, elemsize), dtype=torch.uint8, device=self.device)
+        vn, vE, vstride = _rows_2d(values, "values", self.device)
+        if (vn, vE) != (m, elemsize):
+            raise ValueError(f"values must have shape [{m}, {elemsize}], got {tuple(values.shape)}")
+        if status is None:
+            status = torch.full((m,), 2, dtype=torch.uint8, device=self.device)
+        _need(status, "status", torch.uint8, self.device, shape=(m,))
+        if mbits is not None:
+            _need(mbits, "mbits", torch.int64, self.device, shape=(m,))
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_get_keys_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(keys), L,
+                                                 key_slot, m, _dptr(values), elemsize, vstride, _opt(mbits),
+                                                 _dptr(status), g.stream), "pdht_table_get_keys_dev")
+        return values, status
+
     def counts_dev(self, out=None, stream=None):
         """The four counters as an int64 [4] CUDA tensor, asynchronously."""
         torch = _torch()
@@ -1336,8 +1436,9 @@ class DeviceTable:
 
     def counts(self):
         """(entries stored, records dropped, batches applied -- put, update,
-        cswap, inserting accumulate and add --, slots inspected by puts,
-        inserting accumulates and adds); the last three cumulative.
+        cswap, inserting accumulate, add and keyed put --, slots inspected by
+        puts, inserting accumulates, adds and keyed puts); the last three
+        cumulative.
         Host-synchronous."""
         return tuple(int(x) for x in self.counts_dev().cpu().tolist())
 
