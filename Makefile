@@ -31,17 +31,17 @@ CFLAGS_SHIM = -std=c99 -O3 -fPIC -fvisibility=hidden -Wall -Wextra -Iinclude
 HIP_HDR := pdht_amd/csrc/city_core.h pdht_amd/csrc/kernels.h pdht_amd/csrc/runtime.h \
            pdht_amd/csrc/bucket.h pdht_amd/csrc/launch.h include/pdht_hip.h include/pdht_hip_put.h \
            include/pdht_hip_table.h include/pdht_hip_table_iter.h include/pdht_hip_table_rmw.h include/pdht_hip_table_acc.h \
-           include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_table_keys.h include/pdht_hip_plan.h \
-           include/pdht_city.h
+           include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_table_keys.h \
+           include/pdht_hip_table_keys_rmw.h include/pdht_hip_plan.h include/pdht_city.h
 HDR_PRODUCT := $(wildcard pdht_amd/csrc/product/*.h)
 HDR_TUNING := $(wildcard pdht_amd/csrc/tuning/*.h) pdht_amd/csrc/pdht_hip_tuning.h
 SHIM_HDR := include/pdht_hash.h include/pdht_hip.h include/pdht_hip_put.h include/pdht_hip_table.h \
             include/pdht_hip_table_iter.h include/pdht_hip_table_rmw.h include/pdht_hip_table_acc.h \
-            include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_table_keys.h include/pdht_hip_plan.h \
-            include/pdht_city.h
+            include/pdht_hip_table_add.h include/pdht_hip_table_reduce.h include/pdht_hip_table_keys.h \
+            include/pdht_hip_table_keys_rmw.h include/pdht_hip_plan.h include/pdht_city.h
 # the C-ABI in translation units that build in parallel (make -j)
 HIP_UNITS := pdht_hip pdht_fixed64 pdht_fixed128 pdht_var pdht_host pdht_bucket pdht_rows pdht_table pdht_table_iter \
-             pdht_table_rmw pdht_table_add pdht_table_reduce pdht_table_keys
+             pdht_table_rmw pdht_table_add pdht_table_reduce pdht_table_keys pdht_table_keys_rmw
 OBJ_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.o) $(LIBDIR)/city_host.o
 OBJ_TUN_ENG := $(HIP_UNITS:%=$(LIBDIR)/%.tun.o) $(LIBDIR)/city_host.o $(LIBDIR)/pdht_tuning.tun.o
 OBJ     := $(OBJ_ENG) $(LIBDIR)/pdht_hash.o
@@ -70,7 +70,9 @@ $(LIBDIR)/pdht_table_iter.o $(LIBDIR)/pdht_table_iter.tun.o: $(TABLE_HDR) pdht_a
 $(LIBDIR)/pdht_table_rmw.o $(LIBDIR)/pdht_table_rmw.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_rmw.h
 $(LIBDIR)/pdht_table_add.o $(LIBDIR)/pdht_table_add.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_add.h
 $(LIBDIR)/pdht_table_reduce.o $(LIBDIR)/pdht_table_reduce.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_acc.h
-$(LIBDIR)/pdht_table_keys.o $(LIBDIR)/pdht_table_keys.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_keys.h
+$(LIBDIR)/pdht_table_keys.o $(LIBDIR)/pdht_table_keys.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_keys.h pdht_amd/csrc/table_keys_host.h
+$(LIBDIR)/pdht_table_keys_rmw.o $(LIBDIR)/pdht_table_keys_rmw.tun.o: $(TABLE_HDR) pdht_amd/csrc/table_keys.h pdht_amd/csrc/table_keys_host.h \
+    pdht_amd/csrc/table_rmw.h pdht_amd/csrc/table_keys_rmw.h
 $(foreach u,pdht_fixed64 pdht_fixed128 pdht_var pdht_host,$(LIBDIR)/$(u).o $(LIBDIR)/$(u).tun.o): pdht_amd/csrc/launch.h
 $(LIBDIR)/pdht_host.o $(LIBDIR)/pdht_host.tun.o: pdht_amd/csrc/host_chunks.h
 

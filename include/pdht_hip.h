@@ -242,6 +242,8 @@ int pdht_hip_key_stream_var_dev(const void *bytes, size_t nbytes, const uint64_t
 #include "pdht_hip_table_reduce.h"
 /* Put and get by key on the table, for keys and values already on its device: no records. */
 #include "pdht_hip_table_keys.h"
+/* Update, insert-if-absent and compare-and-swap by key: the local route's write operations. */
+#include "pdht_hip_table_keys_rmw.h"
 /* The 64-B kernel's launch plan and tile order (host arithmetic). */
 #include "pdht_hip_plan.h"
 

@@ -114,9 +114,10 @@ int pdht_table_get_dev(const void *table, uint64_t capacity, size_t rowbytes,
 /* counts4[0..3] (device, 8-byte aligned) = entries stored / records dropped,
  * cumulative / batches that used the winner words (put, the update and
  * cswap of pdht_hip_table_rmw.h, the inserting accumulate of
- * pdht_hip_table_acc.h, the add of pdht_hip_table_add.h and the keyed put of
- * pdht_hip_table_keys.h) / slots inspected by puts, inserting accumulates,
- * adds and keyed puts, cumulative (a retry on one slot after a lost
+ * pdht_hip_table_acc.h, the add of pdht_hip_table_add.h, the keyed put of
+ * pdht_hip_table_keys.h and the keyed update, add and cswap of
+ * pdht_hip_table_keys_rmw.h) / slots inspected by puts, inserting accumulates,
+ * adds, keyed puts and keyed adds, cumulative (a retry on one slot after a lost
  * compare-and-swap is not a new slot). */
 int pdht_table_counts_dev(const void *table, uint64_t *counts4, pdht_hip_stream_t stream);
 

@@ -35,8 +35,9 @@
  *                     and counts4[2] by one: the call takes a batch number
  *                     ("batches that used the winner words": put, update,
  *                     cswap, the inserting accumulate, the add of
- *                     pdht_hip_table_add.h and the keyed put of
- *                     pdht_hip_table_keys.h).
+ *                     pdht_hip_table_add.h, the keyed put of
+ *                     pdht_hip_table_keys.h and the keyed update, add and
+ *                     cswap of pdht_hip_table_keys_rmw.h).
  * The region is `elems` elements of `datatype` at value_offset inside the row,
  * at the same place in the record's row (record + 24) and in the table's row.
  *

@@ -38,7 +38,8 @@
  * created, [1] += records dropped, [3] += slots inspected, and [2] += 1: the
  * call uses the per-slot winner words and takes a batch number, so it counts
  * among the 2^32 batches that used the winner words (put, update, cswap, the
- * inserting accumulate, this add and the keyed put of pdht_hip_table_keys.h)
+ * inserting accumulate, this add, the keyed put of pdht_hip_table_keys.h
+ * and the keyed update, add and cswap of pdht_hip_table_keys_rmw.h)
  * which a table takes between two pdht_table_init_dev calls.
  *
  * Calls on one stream are ordered by the stream; concurrent calls on one

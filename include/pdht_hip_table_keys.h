@@ -60,7 +60,8 @@ extern "C" {
  * dropped).  Counters, the put's: counts4[0] += entries created, [1] += keys
  * dropped, [3] += slots inspected, and [2] += 1: the call uses the per-slot
  * winner words and takes a batch number, so it counts among the 2^32 batches
- * (put, update, cswap, inserting accumulate, add, keyed put) a table takes
+ * (put, update, cswap, inserting accumulate, add, keyed put, and the keyed
+ * update, add and cswap of pdht_hip_table_keys_rmw.h) a table takes
  * between two pdht_table_init_dev calls.
  * status (may be NULL), one uint8 per key: 0 stored / 1 superseded by a later
  * key of the batch with the same mbits / 2 dropped, table full.

@@ -35,8 +35,9 @@
  * pdht_table_counts_dev is "batches that used the winner words (put, update,
  * cswap)", and a table takes 2^32 such batches, of all three kinds together,
  * between two pdht_table_init_dev calls -- together also with the inserting
- * accumulate of pdht_hip_table_acc.h, the add of pdht_hip_table_add.h and
- * the keyed put of pdht_hip_table_keys.h, which take their batch numbers from
+ * accumulate of pdht_hip_table_acc.h, the add of pdht_hip_table_add.h,
+ * the keyed put of pdht_hip_table_keys.h and the keyed update, add and cswap
+ * of pdht_hip_table_keys_rmw.h, which take their batch numbers from
  * the same word.  Calls on one stream
  * are ordered by the stream; concurrent calls on one table from different
  * streams are undefined.  Each call is two kernels with nothing but the kernel boundary

@@ -37,6 +37,7 @@ __all__ = [
     "bucket_record_bytes", "bucket_workspace_bytes", "WeakHashLen32WithSeeds", "WeakHashLen32WithSeeds6",
     "tuning", "last_kernel", "mpi_lib", "table_bytes", "table_reply_bytes", "DeviceTable", "get_resolve",
     "table_export_workspace_bytes", "table_reduce_workspace_bytes", "table_put_keys_workspace_bytes",
+    "table_update_keys_workspace_bytes", "table_add_keys_workspace_bytes", "table_cswap_keys_workspace_bytes",
 ]
 
 K2 = 0x9AE16A3B2F90404F  # city.c:96 (CityHash64WithSeed's seed0)
@@ -156,6 +157,12 @@ def _declare(L, tuning=False):
         "pdht_table_put_keys_workspace_bytes": (C.c_size_t, [_S]),
         "pdht_table_put_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _S, _V, _S, _V, _V, _V]),
         "pdht_table_get_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _S, _V, _S, _S, _V, _V, _V]),
+        "pdht_table_update_keys_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_update_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _S, _V, _S, _V, _V, _V]),
+        "pdht_table_add_keys_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_add_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _V, _S, _S, _S, _V, _S, _V, _V, _V]),
+        "pdht_table_cswap_keys_workspace_bytes": (C.c_size_t, [_S]),
+        "pdht_table_cswap_keys_dev": (C.c_int, [_V, _U64, _S, _V, _S, _S, _S, _U64, _U64, _V, _S, _V, _S, _V, _V]),
         "CityHash64": (_U64, [_V, _S]),
         "CityHash64WithSeed": (_U64, [_V, _S, _U64]),
         "CityHash64WithSeeds": (_U64, [_V, _S, _U64, _U64]),
@@ -919,7 +926,9 @@ def scatter_rows(src, index, out=None, stream=None, check=True):
 #   (include/pdht_hip_table_reduce.h: min, max, and, or, xor beside the sum)
 #   local: DeviceTable.put_keys(keys, values) / DeviceTable.get_keys(keys, E) -- keys and values already on
 #        the table's device: no records, no replies, no sort
-#   (include/pdht_hip_table_keys.h: byte for byte the put and the get flow at nranks = 1)
+#        DeviceTable.update_keys(keys, values) / add_keys(keys, values) / cswap_keys(keys, word_offset, compare,
+#        desired) -- the update, create and claim flows the same way
+#   (include/pdht_hip_table_keys.h, pdht_hip_table_keys_rmw.h: byte for byte the record flows at nranks = 1)
 def table_bytes(capacity: int, rowbytes: int) -> int:
     """Bytes of a DeviceTable's storage: 64 + (capacity + 1) * (16 + rowbytes).
     capacity: a power of two in 64 .. 2^31; rowbytes: a multiple of 8, >= 8."""
@@ -975,6 +984,28 @@ def table_put_keys_workspace_bytes(m: int) -> int:
     if not 0 <= m < (1 << 32):
         raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
     return lib().pdht_table_put_keys_workspace_bytes(m)
+
+
+def table_update_keys_workspace_bytes(m: int) -> int:
+    """Bytes of workspace DeviceTable.update_keys needs for m keys: 4*m."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_update_keys_workspace_bytes(m)
+
+
+def table_add_keys_workspace_bytes(m: int) -> int:
+    """Bytes of workspace DeviceTable.add_keys needs for m keys: 4*m + m
+    rounded up to 4."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_add_keys_workspace_bytes(m)
+
+
+def table_cswap_keys_workspace_bytes(m: int) -> int:
+    """Bytes of workspace DeviceTable.cswap_keys needs for m keys: 4*m."""
+    if not 0 <= m < (1 << 32):
+        raise ValueError(f"m {m} must be in 0 .. 2^32 - 1")
+    return lib().pdht_table_cswap_keys_workspace_bytes(m)
 
 
 # the reduce's operations (include/pdht_hip_table_reduce.h)
@@ -1313,8 +1344,19 @@ class DeviceTable:
         Nothing is inserted.  out: a uint8 [m, 16] tensor or row-strided view,
         8-byte aligned with a stride that is a multiple of 8; workspace:
         uint8, >= 4*m bytes (allocated if None)."""
-        torch = _torch()
         m, ptr, stride = self._requests(mbits_or_records)
+        pair, out, ostride = self._cswap_args(m, word_offset, compare, desired, out)
+        workspace = self._workspace_arg(workspace, lib().pdht_table_cswap_workspace_bytes(m))
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_cswap_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
+                                              stride, m, word_offset, pair[0], pair[1], _dptr(out), ostride,
+                                              _dptr(workspace), workspace.numel(), g.stream), "pdht_table_cswap_dev")
+        return out
+
+    def _cswap_args(self, m, word_offset, compare, desired, out):
+        """The arguments that cswap and cswap_keys share -> ((compare,
+        desired) as 64-bit patterns, out, its row stride in bytes)."""
+        torch = _torch()
         if not isinstance(word_offset, int) or word_offset < 0 or word_offset % 8 or \
                 word_offset + 8 > self.rowbytes:
             raise ValueError(f"word_offset must be a multiple of 8 in 0 .. {self.rowbytes - 8}, got {word_offset}")
@@ -1330,24 +1372,25 @@ class DeviceTable:
             raise ValueError(f"out must have shape [{m}, 16], got {tuple(out.shape)}")
         if ostride % 8 or out.data_ptr() % 8:
             raise ValueError("out must be 8-byte aligned with a row stride that is a multiple of 8")
-        workspace = self._workspace_arg(workspace, lib().pdht_table_cswap_workspace_bytes(m))
-        with _on(self.device, stream) as g:
-            _check(lib().pdht_table_cswap_dev(_dptr(self.storage), self.capacity, self.rowbytes, C.c_void_p(ptr),
-                                              stride, m, word_offset, pair[0], pair[1], _dptr(out), ostride,
-                                              _dptr(workspace), workspace.numel(), g.stream), "pdht_table_cswap_dev")
-        return out
+        return pair, out, ostride
 
-    # ---- put and get by key (include/pdht_hip_table_keys.h) ----
+    # ---- by key (include/pdht_hip_table_keys.h, pdht_hip_table_keys_rmw.h) ----
 
-    def _keys_arg(self, keys, elemsize, key_slot):
-        """-> (m, keysize) of a batch of packed keys whose rows of `elemsize`
-        value bytes behind a key slot are this table's rows."""
+    def _packed_keys_arg(self, keys, route):
+        """-> (m, keysize) of a batch of packed keys of 1 .. 64 bytes; route:
+        where longer keys go, for the message."""
         m, L, kstride = _keys_2d(keys)
         if keys.device != self.device or kstride != L:
             raise ValueError(f"keys must be packed and on {self.device}")
         if not 1 <= L <= 64:
-            raise ValueError(f"keys must have 1 .. 64 bytes, got {L}: longer keys go through bucket_put_records "
-                             "and put_records (get: bucket_records, get, get_resolve)")
+            raise ValueError(f"keys must have 1 .. 64 bytes, got {L}: longer keys go through {route}")
+        return m, L
+
+    def _keys_arg(self, keys, elemsize, key_slot):
+        """-> (m, keysize) of a batch of packed keys whose rows of `elemsize`
+        value bytes behind a key slot are this table's rows."""
+        m, L = self._packed_keys_arg(keys, "bucket_put_records and put_records (get: bucket_records, get, "
+                                           "get_resolve)")
         if not isinstance(elemsize, int) or isinstance(elemsize, bool) or elemsize < 1:
             raise ValueError("elemsize must be >= 1")
         if not isinstance(key_slot, int) or isinstance(key_slot, bool) or key_slot < 0 or \
@@ -1382,19 +1425,68 @@ class DeviceTable:
         mbits.  Returns status, or (status, mbits) with mbits.  workspace:
         uint8, >= table_put_keys_workspace_bytes(m) bytes (allocated if None).
         counts()[2] advances by one."""
+        return self._apply_keys("put", keys, values, key_slot, status, mbits, workspace, stream)
+
+    def _apply_keys(self, kind, keys, values, key_slot, status, mbits, workspace, stream):
         nv, E, vstride = _rows_2d(values, "values", self.device)
         m, L = self._keys_arg(keys, E, key_slot)
         if nv != m:
             raise ValueError(f"values must have one row per key: {nv} rows for {m} keys")
         status = self._status_arg(status, m)
         mbits = self._mbits_arg(mbits, m)
-        workspace = self._workspace_arg(workspace, lib().pdht_table_put_keys_workspace_bytes(m))
+        workspace = self._workspace_arg(workspace, getattr(lib(), f"pdht_table_{kind}_keys_workspace_bytes")(m))
         with _on(self.device, stream) as g:
-            _check(lib().pdht_table_put_keys_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(keys), L,
-                                                 key_slot, _dptr(values), E, vstride, m, _dptr(workspace),
-                                                 workspace.numel(), _opt(mbits), _opt(status), g.stream),
-                   "pdht_table_put_keys_dev")
+            name = f"pdht_table_{kind}_keys_dev"
+            _check(getattr(lib(), name)(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(keys), L, key_slot,
+                                        _dptr(values), E, vstride, m, _dptr(workspace), workspace.numel(),
+                                        _opt(mbits), _opt(status), g.stream), name)
         return status if mbits is None else (status, mbits)
+
+    def update_keys(self, keys, values, *, key_slot: int = 0, status=True, mbits=None, workspace=None, stream=None):
+        """Overwrites the rows under keys that have an entry
+        (pdht_table_update_keys_dev): what bucket_put_records(keys, values,
+        nranks=1, key_slot=key_slot) -> update_records leaves, table, status
+        and counts() byte for byte, without records.  Matching is by mbits =
+        CityHash64(key) alone; the whole row -- key, zeros up to the key slot,
+        value, zeros up to 8 -- replaces the entry's, and the last key of an
+        mbits leaves its row.  Nothing is inserted.  Arguments and return as
+        put_keys; status: 0 stored / 1 superseded / 3 not found.  workspace:
+        uint8, >= table_update_keys_workspace_bytes(m) bytes (allocated if
+        None).  counts()[2] advances by one."""
+        return self._apply_keys("update", keys, values, key_slot, status, mbits, workspace, stream)
+
+    def add_keys(self, keys, values, *, key_slot: int = 0, status=True, mbits=None, workspace=None, stream=None):
+        """Inserts values[i] under keys[i] where no entry is
+        (pdht_table_add_keys_dev): what bucket_put_records(keys, values,
+        nranks=1, key_slot=key_slot) -> add_records leaves, table, status and
+        counts()[:3] byte for byte, without records.  The first key of a new
+        mbits wins, an entry that is present keeps every byte.  Arguments and
+        return as put_keys; status: 0 created by this key / 4 exists / 2
+        dropped, table full.  There are no replies: get_keys reads the
+        entries.  workspace: uint8, >= table_add_keys_workspace_bytes(m) bytes
+        (allocated if None).  counts() advance as for add_records."""
+        return self._apply_keys("add", keys, values, key_slot, status, mbits, workspace, stream)
+
+    def cswap_keys(self, keys, word_offset: int, compare: int, desired: int, *, out=None, mbits=None, workspace=None,
+                   stream=None):
+        """cswap by key (pdht_table_cswap_keys_dev): what bucket_records(keys,
+        1) -> cswap(records, word_offset, compare, desired) leaves, table,
+        replies and counts() byte for byte, without records.  keys [m, L]
+        packed uint8, L in 1 .. 64, matched by mbits = CityHash64(key) alone.
+        word_offset, compare, desired and out as in cswap; reply i is key i's.
+        mbits as in put_keys.  Returns the replies uint8 [m, 16], or (replies,
+        mbits) with mbits.  workspace: uint8, >=
+        table_cswap_keys_workspace_bytes(m) bytes (allocated if None)."""
+        m, L = self._packed_keys_arg(keys, "bucket_records and cswap")
+        pair, out, ostride = self._cswap_args(m, word_offset, compare, desired, out)
+        mbits = self._mbits_arg(mbits, m)
+        workspace = self._workspace_arg(workspace, lib().pdht_table_cswap_keys_workspace_bytes(m))
+        with _on(self.device, stream) as g:
+            _check(lib().pdht_table_cswap_keys_dev(_dptr(self.storage), self.capacity, self.rowbytes, _dptr(keys), L,
+                                                   m, word_offset, pair[0], pair[1], _dptr(out), ostride,
+                                                   _dptr(workspace), workspace.numel(), _opt(mbits), g.stream),
+                   "pdht_table_cswap_keys_dev")
+        return out if mbits is None else (out, mbits)
 
     def get_keys(self, keys, elemsize: int, *, key_slot: int = 0, values=None, status=None, mbits=None, stream=None):
         """Reads the values under keys (pdht_table_get_keys_dev): what
@@ -1436,9 +1528,9 @@ class DeviceTable:
 
     def counts(self):
         """(entries stored, records dropped, batches applied -- put, update,
-        cswap, inserting accumulate, add and keyed put --, slots inspected by
-        puts, inserting accumulates, adds and keyed puts); the last three
-        cumulative.
+        cswap, inserting accumulate, add and the keyed put, update, add and
+        cswap --, slots inspected by puts, inserting accumulates, adds, keyed
+        puts and keyed adds); the last three cumulative.
         Host-synchronous."""
         return tuple(int(x) for x in self.counts_dev().cpu().tolist())
 

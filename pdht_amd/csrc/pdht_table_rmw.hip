@@ -80,14 +80,7 @@ static int table_cswap(void *table, u64 capacity, size_t rowbytes, const void *m
   c.desired = desired;
   c.replies = static_cast<uint8_t *>(replies);
   c.reply_stride = reply_stride;
-  const bool wide = (((uintptr_t)replies | reply_stride) & 15) == 0;
-  const bool nt = hook_table_reply_nt(kTableReplyNt);
-  if (wide)
-    nt ? k_table_cswap<true, true><<<grid, kBlock, 0, st>>>(c)
-       : k_table_cswap<true, false><<<grid, kBlock, 0, st>>>(c);
-  else
-    nt ? k_table_cswap<false, true><<<grid, kBlock, 0, st>>>(c)
-       : k_table_cswap<false, false><<<grid, kBlock, 0, st>>>(c);
+  launch_table_cswap(c, hook_table_reply_nt(kTableReplyNt), grid, st);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -178,6 +178,7 @@ struct KeysWriteArgs {
   uint8_t *status;  // may be null
   u32 np;           // pieces of a row
   u32 gshift;       // log2 of the lane group (G = the power of two >= np, at most 64)
+  u32 absent;       // status of a key without a slot: 2 dropped (put_keys), 3 not found (update_keys, table_keys_rmw.h)
 };
 
 // P: 16 or 8 bytes per piece of the table's row.  A: keys, keysize, values, value_stride and elemsize are all
@@ -223,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void k_table_write_keys(const KeysWriteArgs
         for (u32 c = l + 64; c < a.np; c += 64)
           st<NT>(piece_load<P, A>(piece_source<P>(a.s, c), row[r]), reinterpret_cast<T *>(d + (u64)c * P));
       }
-      if (a.status && l == 0 && row[r] < a.m) a.status[row[r]] = slot[r] == kTableNoSlot ? 2 : own[r] ? 0 : 1;
+      if (a.status && l == 0 && row[r] < a.m) a.status[row[r]] = slot[r] == kTableNoSlot ? a.absent : own[r] ? 0 : 1;
     }
   }
 }

@@ -103,4 +103,14 @@ __global__ __launch_bounds__(kBlock) void k_table_cswap(const CswapArgs a) {
   }
 }
 
+// k_table_cswap behind the kernel that left slots and winner words (k_table_locate<true>, or
+// k_table_locate_keys of table_keys_rmw.h), on that kernel's grid.  nt: the store policy of the replies.
+static void launch_table_cswap(const CswapArgs &c, bool nt, unsigned grid, hipStream_t st) {
+  const bool wide = (((uintptr_t)c.replies | c.reply_stride) & 15) == 0;
+  if (wide)
+    nt ? k_table_cswap<true, true><<<grid, kBlock, 0, st>>>(c) : k_table_cswap<true, false><<<grid, kBlock, 0, st>>>(c);
+  else
+    nt ? k_table_cswap<false, true><<<grid, kBlock, 0, st>>>(c) : k_table_cswap<false, false><<<grid, kBlock, 0, st>>>(c);
+}
+
 }  // namespace pdht
